@@ -15,16 +15,23 @@ used, and WORLD_SIZE must equal --gpus): one independent chain per GPU
 (seed 42 + rank, Philox chain id = rank); no collective inside the timed
 region; value = total chain-steps / max-over-ranks wall time.
 
-Prints one JSON line (rank 0).  Extra fields: hbm_gbs (algorithmic), the
-per-kernel-kind table with HIP-event timings, roofline of the dominant
-kernel, and the CPU baseline (the oracle's op-for-op torch-CPU restatement of
-the reference update, timed on this host on a bounded sample).  After the
+Prints one JSON line (rank 0).  A plain run sets up, tunes the launch, warms
+up, times the steps and prints the line: value, ms_per_step, hbm_gbs
+(algorithmic), the per-kernel-kind table with the timed region's own
+HIP-event timings and the roofline of the dominant kernel.  `--dump-outputs
+DIR` writes what the last timed step left (theta, the momentum, every cycle's
+moment pair; a fixed seeded sample of vectors too large to store whole) as
+DIR/<name>.npy right after the timed region.
+
+`--full` adds everything that takes runs of its own: the CPU baseline (the
+oracle's op-for-op torch-CPU restatement of the reference update, timed on
+this host on a bounded sample) and, after the
 timed region (never inside it): every sweep's `mix_ceiling` (the fastest
 arithmetic-free form of its own access pattern on its own buffers: bare,
 pipelined, paced and, for cSGHMC, the kernel's own loop without its update),
 the explore on the Runners' per-tensor gradients, the other configurations'
 sweeps (`methods`), and end-to-end ViT-L/32 steps with an interleaved
-autograd-only leg (`e2e`, informational).
+autograd-only leg (`e2e`, informational); at N > 1 the evaluation collective.
 """
 from __future__ import annotations
 
@@ -90,7 +97,41 @@ def parse():
                          "packets between kernels): at 1 the line's ms_per_step read 1.0239-1.0248 "
                          "vs 1.0186-1.0191 at 10 on one box, the kernel averages unchanged")
     ap.add_argument("--traffic", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run everything that takes runs of its "
+                         "own: the steady-collect and per-tensor-gradient timings, aux_kernels, "
+                         "every mix_ceiling, the other methods' lines, the e2e legs, the CPU "
+                         "baseline and (N > 1) the evaluation collective; the --no-* switches "
+                         "and --e2e-steps select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state the last step left as "
+                         "DIR/<name>.npy (float32; rank 0's chain): theta, mom, each cycle's "
+                         "m1 / m2 and the method's extra vectors.  Vectors too large to store "
+                         "whole are sampled at fixed seeded indices (48 MiB in all)")
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # all of --dump-outputs' files together
+DUMP_SEED = 20240613
+
+
+def dump_outputs(path, vectors):
+    """Write `vectors` ({name: flat fp32 device tensor}) as path/<name>.npy.
+    A vector longer than its share of DUMP_BUDGET_BYTES is sampled at indices
+    drawn once from a fixed seed (sorted, the same for every vector of one
+    length), so two builds run with the same arguments write comparable files."""
+    os.makedirs(path, exist_ok=True)
+    per = max(1, DUMP_BUDGET_BYTES // (4 * max(1, len(vectors))))
+    index = {}
+    for name, v in vectors.items():
+        v = v.detach().reshape(-1)
+        k = v.numel()
+        if k > per:
+            if k not in index:
+                idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, k, per))
+                index[k] = torch.from_numpy(idx).to(v.device)
+            v = v.index_select(0, index[k])
+        np.save(os.path.join(path, f"{name}.npy"), v.to(torch.float32).cpu().numpy())
 
 
 def pool_timing(chains, st, world, dist, out):
@@ -954,8 +995,16 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert torch.isfinite(st.theta[:1 << 20]).all()
+    if a.dump_outputs and rank == 0:
+        # what the last timed step left, before anything below touches the state
+        vecs = {"theta": st.theta, "mom": st.mom}
+        if adam:
+            vecs.update({k: st.extra[k] for k in ("adam_m", "adam_v", "sgd_buf")})
+        for c in sorted(m1s):
+            vecs[f"cycle{c}_m1"], vecs[f"cycle{c}_m2"] = m1s[c], m2s[c]
+        dump_outputs(a.dump_outputs, vecs)
     collective = None
-    if dist is not None:
+    if a.full and dist is not None:
         # informational, after the timed region: the one cross-chain exchange
         # (posterior-predictive average of a [128, 1000] fp32 batch, bayesdll_amd.chains)
         from bayesdll_amd import chains
@@ -1044,10 +1093,10 @@ def main():
     # after the timed region, on the same state: the steady-state collect over
     # enough launches for percentiles, and the explore step on per-tensor
     # gradients (the Runners' default gradient mode)
-    if not sgld and m1s:
+    if a.full and not sgld and m1s:
         table["collect_steady"] = dict(collect_steady_timing(st, m1s, m2s, spc, rank),
                                        launches=0, timed_region=False)
-    if not sgld and a.grad_mode == "flat":
+    if a.full and not sgld and a.grad_mode == "flat":
         ex = explore_tensor_grad_timing(st)
         ex["vs_flat_explore"] = round(ex["avg_ms"] / table["explore"]["avg_ms"], 4) \
             if "explore" in table else None
@@ -1055,8 +1104,9 @@ def main():
     out["methodology"] = {
         "timed_kinds": sorted(set(kinds)),
         "event_stride": timer.stride,
-        "collect_init": "timed after the region (aux_kernels.collect_init): every cycle's Welford "
-                        "pair is initialised before it",
+        "collect_init": "timed after the region (--full: aux_kernels.collect_init): every cycle's "
+                        "Welford pair is initialised before it",
+        "full": a.full,
         "post_region_kinds": [k for k, v in table.items() if v.get("timed_region") is False],
         "since": "round 3 (rounds 1-2: every launch bracketed, the init collect inside the region)"}
     if dist is not None:
@@ -1072,6 +1122,12 @@ def main():
         out["distributed"] = {"world_size": dist.get_world_size(), "backend": dist.get_backend(),
                               "device_count": devices[0]["device_count"],
                               "distinct_devices": len({(d["pci"], d["uuid"]) for d in devices})}
+    if not a.full:  # a plain run ends here: the line of the timed region alone
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     if not a.no_aux:
         out["aux_kernels"] = aux_kernels(st)
         if not sgld and m1s:

@@ -101,6 +101,32 @@ def _bench_module():
     return mod
 
 
+def test_dump_outputs_writes_float32_within_its_budget_and_repeats(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): one float32 .npy per vector; a
+    vector within its share of the budget whole, a longer one at sorted sample
+    indices that depend only on the seed and its length, so a second call
+    writes the same files."""
+    import numpy as np
+    import torch
+    b = _bench_module()
+    monkeypatch.setattr(b, "DUMP_BUDGET_BYTES", 3 * 4 * 1000)  # 1000 elements per vector
+    g = torch.Generator().manual_seed(3)
+    vecs = {"theta": torch.randn(5000, generator=g), "mom": torch.randn(5000, generator=g),
+            "small": torch.randn(777, generator=g)}
+    b.dump_outputs(str(tmp_path / "a"), vecs)
+    b.dump_outputs(str(tmp_path / "b"), vecs)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in vecs}
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["mom.npy", "small.npy", "theta.npy"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= b.DUMP_BUDGET_BYTES
+    assert np.array_equal(got["small"], vecs["small"].numpy())
+    idx = np.sort(np.random.default_rng(b.DUMP_SEED).integers(0, 5000, 1000))
+    assert np.array_equal(got["theta"], vecs["theta"].numpy()[idx])
+    assert np.array_equal(got["mom"], vecs["mom"].numpy()[idx])
+    for k in vecs:
+        assert np.array_equal(got[k], np.load(tmp_path / "b" / f"{k}.npy"))
+
+
 def test_distinct_device_check_refuses_shared_or_missing_gpus():
     """bench.check_distinct_devices: under RCCL every rank must report its own
     GPU (PCI address + UUID) and the node must show at least N devices; the

@@ -33,8 +33,8 @@ def _free_port():
     return port
 
 
-BENCH_ARGS = ["--steps", "20", "--warmup", "5", "--backbone", "resnet101",
-              "--no-autotune", "--e2e-steps", "0"]
+BENCH_ARGS = ["--full", "--steps", "20", "--warmup", "5", "--backbone", "resnet101",
+              "--no-autotune", "--e2e-steps", "0"]  # --full: the evaluation collective
 
 
 # ("torchrun", 8): the driver's own N=8 command shape (torch.distributed.run

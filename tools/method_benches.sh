@@ -11,7 +11,7 @@ run() {  # name args...
   timeout -k 10 300 python bench.py "$@" > gpurun_out/methods/$name.json 2> gpurun_out/methods/$name.err || exit 1
   python3 -c "import json; d=json.load(open('gpurun_out/methods/$name.json')); r=d['roofline']; mc=r.get('mix_ceiling') or {}; print('$name', d['value'], r['kernel'], d['kernels'][r['kernel']]['avg_ms'], r['frac'], 'bare', mc.get('best_ms'), 'of_ceiling', mc.get('of_ceiling'))"
 }
-run csghmc_vit
-run sgld_rn101 --backbone resnet101 --method sgld --no-cpu-baseline --e2e-steps 0
-run sgld_vit --method sgld --no-cpu-baseline --e2e-steps 0
-run adam_vit --method adam_sghmc --no-cpu-baseline --e2e-steps 0
+run csghmc_vit --full
+run sgld_rn101 --full --backbone resnet101 --method sgld --no-cpu-baseline --e2e-steps 0
+run sgld_vit --full --method sgld --no-cpu-baseline --e2e-steps 0
+run adam_vit --full --method adam_sghmc --no-cpu-baseline --e2e-steps 0
