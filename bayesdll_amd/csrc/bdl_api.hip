@@ -518,6 +518,25 @@ size_t run_lds_bytes(const bdl_step_args* s) {
   return (size_t)s->nruns * (sizeof(bdl_run) + (s->grad_base ? sizeof(int64_t) : 0));
 }
 
+// The Philox counter carries the low 32 bits of the float4 group index and of
+// the chain id (philox_normal4): a launch that draws noise must keep both
+// below 2^32, or it would silently draw another group's / chain's stream
+// (chain 2^32 + 3 is chain 3).  groups: (n + 3) / 4; offset: philox_offset;
+// chain_groups > 0: stacked chains, keyed chain .. chain + (their number) - 1.
+int check_philox_range(const char* what, int64_t n, uint64_t offset, uint64_t chain,
+                       uint64_t chain_groups) {
+  constexpr uint64_t k2p32 = 1ull << 32;
+  const uint64_t groups = (uint64_t)((n + 3) / 4);  // n >= 0: below 2^61
+  if (offset > k2p32 || groups + offset > k2p32)
+    return fail(BDL_ERR_ARG, std::string(what) + ": Philox noise needs every float4 group index "
+                "below 2^32 (n / 4 + philox_offset)");
+  const uint64_t nchains = chain_groups ? (groups + offset + chain_groups - 1) / chain_groups : 0;
+  if (chain >= k2p32 || chain + nchains >= k2p32)
+    return fail(BDL_ERR_ARG, std::string(what) + ": Philox noise needs every chain id below 2^32 "
+                "(chain, plus the number of stacked chains)");
+  return BDL_OK;
+}
+
 // Shared checks of the run table and the gradient source ("what" prefixes errors).
 int check_runs_and_grad(const bdl_step_args* s, const char* what) {
   if (!s->runs || s->nruns < 1)
@@ -536,6 +555,8 @@ int check_runs_and_grad(const bdl_step_args* s, const char* what) {
        (uint64_t)((s->n + 3) / 4) + s->philox_offset > 0xFFFFFFFFull))
     return fail(BDL_ERR_ARG, std::string(what) + ": stacked chains need every float4 group "
                 "index below 2^32 (chain_groups, n / 4 + philox_offset)");
+  if (s->noise_mode == BDL_NOISE_PHILOX)
+    return check_philox_range(what, s->n, s->philox_offset, s->chain, s->chain_groups);
   return BDL_OK;
 }
 
@@ -1159,6 +1180,9 @@ int bdl_posterior_sample(const bdl_sample_args* s, void* stream) {
       (s->chain_groups > 0xFFFFFFFFull || (uint64_t)((s->n + 3) / 4) > 0xFFFFFFFFull))
     return fail(BDL_ERR_ARG, "bdl_posterior_sample: stacked chains need every float4 group "
                 "index below 2^32");
+  if (s->noise_mode == BDL_NOISE_PHILOX)
+    if (const int rc = check_philox_range("bdl_posterior_sample", s->n, 0, s->chain, s->chain_groups))
+      return rc;
   if (s->blocks_per_cu < 0 || s->blocks_per_cu > 8)
     return fail(BDL_ERR_ARG, "bdl_posterior_sample: blocks_per_cu in [0, 8]");
   if (s->unroll != 0 && s->unroll != 1 && s->unroll != 4)
@@ -1235,6 +1259,7 @@ int bdl_philox_normal(float* out, int64_t n, uint64_t seed, uint64_t chain, uint
   if (n == 0) return BDL_OK;
   if (!out) return fail(BDL_ERR_NULL, "bdl_philox_normal: null out");
   if (!aligned16(out)) return fail(BDL_ERR_ALIGN, "bdl_philox_normal: out not 16-B aligned");
+  if (const int rc = check_philox_range("bdl_philox_normal", n, 0, chain, 0)) return rc;
   hipLaunchKernelGGL(bdl_philox_kernel, dim3(grid_for((n + 3) / 4, kBlock * 4)), dim3(kBlock), 0,
                      (hipStream_t)stream, out, n, seed, chain, step);
   const hipError_t err = hipGetLastError();

@@ -168,8 +168,8 @@ typedef struct bdl_step_args {
   float inv_collect_b;
   float pad1;
   uint64_t seed;           /* Philox key                                            */
-  uint64_t chain;          /* chain id (rank)                                        */
-  uint64_t step;           /* global step counter                                    */
+  uint64_t chain;          /* chain id (rank); < 2^32 with BDL_NOISE_PHILOX (below)  */
+  uint64_t step;           /* global step counter (all 64 bits are counted)          */
   /* Gradient in place, per tensor (null: the flat `grad` vector is used).
    * Device array of nruns byte addresses: run r's gradient for flat element i
    * is ((float*)grad_base[r])[i], i.e. grad_base[r] = (address of the tensor's
@@ -189,7 +189,14 @@ typedef struct bdl_step_args {
   /* Philox counter offset, in float4 groups: a launch over the sub-range
    * [4*philox_offset, 4*philox_offset + n) of a chain's flat vectors (all
    * pointers and the run table shifted to it) draws exactly the noise the
-   * whole-vector launch draws there.  0 for whole-vector launches. */
+   * whole-vector launch draws there.  0 for whole-vector launches.
+   * The Philox counter is (group index lo32, chain lo32, step lo32, step
+   * hi32) and the key the 64-bit seed: a BDL_NOISE_PHILOX launch (here, in
+   * bdl_adam_step, bdl_sgld_step_clipped, bdl_posterior_sample and
+   * bdl_philox_normal) whose group indices (n + 3) / 4 + philox_offset would
+   * exceed 2^32, or whose chain id — for stacked chains, chain + the number
+   * of chains — reaches 2^32, is refused with BDL_ERR_ARG: it would draw
+   * another group's / chain's stream. */
   uint64_t philox_offset;
   /* Stacked chains (0: the vectors hold one chain).  > 0: they hold
    * consecutive chains of 4*chain_groups elements each — chain k's element j

@@ -216,6 +216,91 @@ def test_entry_points_validate_before_touching_the_device():
     assert b"bdl_adam_step" in h.bdl_last_error()
 
 
+def test_philox_launches_refuse_group_and_chain_ids_that_would_wrap():
+    """The Philox counter carries 32 bits of the float4 group index and of the
+    chain id: a Philox launch that would reach 2^32 in either returns
+    BDL_ERR_ARG (it would draw another group's / chain's noise); the largest
+    ids that fit pass the check.  Host only: fake pointers, and every call
+    here is refused before a launch (the accepted edges by a later check)."""
+    from bayesdll_amd import _lib as L
+    h = L.lib()
+    P32 = 1 << 32
+
+    def step_args(method):
+        a = L.StepArgs()
+        a.theta, a.grad, a.prior_mean, a.runs, a.nruns = 0x1000, 0x2000, 0x5000, 0x4000, 1
+        a.mom = None  # the later check that stops the accepted edges: mom is required
+        if method == L.ADAM_SGHMC:  # (Adam checks mom first: its later check is the SGD buffer)
+            a.mom, a.flags = 0x3000, L.FLAG_MOMENTUM
+        a.n, a.method, a.noise_mode = 8, method, L.NOISE_PHILOX
+        return a
+
+    ad = L.AdamArgs()
+    ad.adam_m, ad.adam_v = 0x7000, 0x8000
+    entries = [
+        ("bdl_sgmcmc_step", lambda a: h.bdl_sgmcmc_step(a, None), L.CSGHMC),
+        ("bdl_sgmcmc_step", lambda a: h.bdl_sgmcmc_step(a, None), L.SGHMC),
+        ("bdl_sgmcmc_step", lambda a: h.bdl_sgmcmc_step(a, None), L.SGLD_GRAD),
+        ("bdl_sgld_step_clipped",
+         lambda a: h.bdl_sgld_step_clipped(a, 1.0, C.c_void_p(0x6000), None), L.SGLD),
+        ("bdl_adam_step", lambda a: h.bdl_adam_step(a, ad, None), L.ADAM_SGHMC),
+    ]
+    for name, call, method in entries:
+        a = step_args(method)
+        a.chain = P32 + 3                                            # would draw chain 3
+        assert call(a) == -3 and b"chain id" in h.bdl_last_error(), name
+        assert name.encode() in h.bdl_last_error()
+        a.chain = P32
+        assert call(a) == -3, name
+        a.chain, a.philox_offset = 3, P32 - 1                        # groups 2 + offset > 2^32
+        assert call(a) == -3 and b"group index" in h.bdl_last_error(), name
+        a.philox_offset = (1 << 64) - 1                              # no overflow in the sum
+        assert call(a) == -3 and b"group index" in h.bdl_last_error(), name
+        a.philox_offset, a.n = 0, 4 * P32 + 1
+        assert call(a) == -3 and b"group index" in h.bdl_last_error(), name
+        # stacked: chain + the number of stacked chains reaches 2^32
+        a.n, a.chain_groups, a.chain = 24, 2, P32 - 3                # 3 chains
+        assert call(a) == -3 and b"chain id" in h.bdl_last_error(), name
+        a.n, a.philox_offset, a.chain = 16, 2, P32 - 3               # groups 2..5: 3 chains
+        assert call(a) == -3 and b"chain id" in h.bdl_last_error(), name
+        # the noise-free / buffer launches draw nothing: no such limit
+        if name != "bdl_adam_step":
+            a.chain_groups, a.philox_offset, a.chain, a.noise_mode = 0, 0, P32 + 3, L.NOISE_NONE
+            if method in (L.CSGHMC, L.SGHMC):
+                assert call(a) == -1 and b"mom is required" in h.bdl_last_error(), name
+        if method not in (L.CSGHMC, L.SGHMC, L.ADAM_SGHMC):
+            continue  # no later check to stop an accepted launch of these
+        # accepted edges: the largest ids that fit reach the later (mom) check
+        a = step_args(method)
+        a.chain = P32 - 1
+        assert call(a) == -1, name
+        a.chain, a.philox_offset = 0, P32 - 2                        # last group index 2^32 - 1
+        assert call(a) == -1, name
+        a.philox_offset, a.chain_groups, a.n, a.chain = 0, 2, 24, P32 - 4   # ids up to 2^32 - 2
+        assert call(a) == -1, name
+
+    sa = L.SampleArgs()
+    sa.n, sa.out, sa.mom1, sa.noise_mode = 8, 0x1000, 0x2000, L.NOISE_PHILOX
+    sa.unroll = 3  # the later check that stops the accepted edges
+    sa.chain = P32
+    assert h.bdl_posterior_sample(sa, None) == -3 and b"chain id" in h.bdl_last_error()
+    sa.chain, sa.chain_groups = P32 - 2, 1                           # 2 stacked chains
+    assert h.bdl_posterior_sample(sa, None) == -3 and b"chain id" in h.bdl_last_error()
+    sa.chain, sa.chain_groups, sa.n = 0, 0, 4 * P32 + 1
+    assert h.bdl_posterior_sample(sa, None) == -3 and b"group index" in h.bdl_last_error()
+    sa.n, sa.chain = 8, P32 - 1
+    assert h.bdl_posterior_sample(sa, None) == -3 and b"unroll" in h.bdl_last_error()
+    sa.chain, sa.chain_groups = P32 - 3, 1
+    assert h.bdl_posterior_sample(sa, None) == -3 and b"unroll" in h.bdl_last_error()
+
+    out = C.c_void_p(0x1000)
+    assert h.bdl_philox_normal(out, 8, 1, P32 + 3, 5, None) == -3
+    assert b"chain id" in h.bdl_last_error()
+    assert h.bdl_philox_normal(out, 8, 1, P32, 5, None) == -3
+    assert h.bdl_philox_normal(out, 4 * P32 + 1, 1, 0, 5, None) == -3
+    assert b"group index" in h.bdl_last_error()
+
+
 def test_other_entry_points_refuse_while_a_graph_redirect_is_active():
     """Only bdl_sgmcmc_step rewrites a captured node: while a redirect is set,
     every other launching entry point launches nothing and says why (a
