@@ -116,6 +116,30 @@ EXPORTS = {
     "bdl_arena_contains": (C.c_int, [C.c_int32, C.c_void_p, C.c_int64]),
 }
 
+
+class DiagSummary(C.Structure):
+    """include/bdl_diag.h bdl_diag_summary (the start of the diagnostic's workspace)."""
+    _fields_ = [("n_eval", C.c_int64), ("n_degenerate", C.c_int64), ("n_nonfinite", C.c_int64),
+                ("argmax", C.c_int64), ("n_above", C.c_int64 * 3), ("rhat_sum", C.c_double),
+                ("rhat_max", C.c_float), ("pad", C.c_float)]
+
+
+class DiagArgs(C.Structure):
+    """include/bdl_diag.h bdl_chain_diag_args."""
+    _fields_ = [("mom1", _fp), ("mom2", _fp), ("pooled_mean", _fp), ("pooled_var", _fp),
+                ("rhat", _fp), ("workspace", _fp), ("n", C.c_int64), ("chain_groups", C.c_uint64),
+                ("chains", C.c_int32), ("var_mode", C.c_int32), ("ratio", C.c_float),
+                ("inv_ratio", C.c_float), ("var_floor", C.c_float), ("c1", C.c_float),
+                ("thresholds", C.c_float * 3), ("blocks_per_cu", C.c_int32)]
+
+
+# include/bdl_diag.h: additive to the ABI, bound next to EXPORTS (which stays
+# the function list of the three original headers)
+DIAG_EXPORTS = {
+    "bdl_chain_diag_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "bdl_chain_diag": (C.c_int, [C.POINTER(DiagArgs), C.c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -133,7 +157,7 @@ def lib():
                     "`make -C bayesdll_amd/csrc` (or __graft_entry__.build()). There is no CPU "
                     "fallback for the fused SG-MCMC step.")
             h = C.CDLL(LIB_PATH)
-            for name, (res, argt) in EXPORTS.items():
+            for name, (res, argt) in list(EXPORTS.items()) + list(DIAG_EXPORTS.items()):
                 fn = getattr(h, name)
                 fn.restype = res
                 fn.argtypes = argt

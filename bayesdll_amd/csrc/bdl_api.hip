@@ -363,17 +363,13 @@ __device__ __forceinline__ f4v sample_noise4(const SArgs& a, int64_t gi) {
 
 template <int VAR, bool M2, bool RECIP>
 __device__ __forceinline__ float sample_var(const SArgs& a, float mj, float qj) {
-  float var;
-  if constexpr (!M2)
-    var = a.var_floor;
-  else if constexpr (VAR == BDL_VAR_RAW_MOMENTS)
-    var = a.ratio * (qj - mj * mj);  // sgld.py:342
-  else if constexpr (VAR == BDL_VAR_WELFORD)
-    var = RECIP ? qj * a.inv_ratio : qj / a.ratio;  // csghmc.py:455
-  else
-    var = qj;
-  if (!(var != var)) var = fmaxf(var, a.var_floor);  // clamp_(min=1e-12); NaN stays NaN
-  return var;
+  if constexpr (!M2) {
+    float var = a.var_floor;
+    if (!(var != var)) var = fmaxf(var, a.var_floor);
+    return var;
+  } else {
+    return posterior_var<VAR, RECIP>(mj, qj, a.ratio, a.inv_ratio, a.var_floor);
+  }
 }
 
 // FLOORED: the host saw var_floor >= 2^-96, so every variance is NaN or at
@@ -830,6 +826,10 @@ MixKernel pick_mix(int nr, int nw, int schedule, int unroll) {
 
 // errors of the other host translation units (bdl_arena.hip)
 void set_last_error(const std::string& msg) { g_last_error = msg; }
+
+// for the launching entry points of the other translation units (bdl_diag.hip)
+bool graph_redirect_active() { return g_redirect_exec != nullptr; }
+int cu_count() { return device_cu_count(); }
 
 }  // namespace bdl
 

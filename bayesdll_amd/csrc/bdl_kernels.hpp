@@ -259,6 +259,25 @@ __device__ __forceinline__ float sdiv(float x, float s, float inv_s) {
     return x / s;
 }
 
+// The variance a posterior draw takes the square root of, from one element's
+// (mean, second-moment source): bdl_posterior_sample's draw and
+// bdl_chain_diag's within-chain variance are this one function.  VAR: where
+// the variance comes from; RECIP: Welford M2 * fl(1/(n-1)) as torch on the
+// device.
+template <int VAR, bool RECIP>
+__device__ __forceinline__ float posterior_var(float mj, float qj, float ratio, float inv_ratio,
+                                               float var_floor) {
+  float var;
+  if constexpr (VAR == BDL_VAR_RAW_MOMENTS)
+    var = ratio * (qj - mj * mj);  // sgld.py:342
+  else if constexpr (VAR == BDL_VAR_WELFORD)
+    var = RECIP ? qj * inv_ratio : qj / ratio;  // csghmc.py:455
+  else
+    var = qj;
+  if (!(var != var)) var = fmaxf(var, var_floor);  // clamp_(min=1e-12); NaN stays NaN
+  return var;
+}
+
 // ---------------------------------------------------------------------------
 // Run table staged in LDS (dynamic, 16 B per run, sized per launch).  The fast
 // path reads the block-uniform attribute of its iteration from LDS, so the

@@ -108,6 +108,13 @@ def alg_bytes_per_elem(a, adam=None):
     return b
 
 
+def diag_bytes_per_elem(chains, outputs):
+    """Algorithmic HBM bytes per evaluated element of one chain_diag sweep
+    (DESIGN §4d): every chain's mom1 and mom2 read once, 4 B per requested
+    output vector written."""
+    return 8 * int(chains) + 4 * int(outputs)
+
+
 class StepTimer:
     """Sampled HIP-event timing of the fused update launches (BDL_STEP_TIMING=k:
     every k-th launch), on the launch stream; summary() once per epoch gives
@@ -371,6 +378,105 @@ def posterior_sample(out, mom1, mom2, *, var_mode, ratio=1.0, var_floor=1e-12, n
     a.blocks_per_cu, a.unroll = (int(x) for x in (geometry or (0, 0)))
     L.check(L.lib().bdl_posterior_sample(a, L.current_stream_handle(out.device)),
             "bdl_posterior_sample")
+
+
+DIAG_OUTPUTS = ("pooled_mean", "pooled_var", "rhat")
+_DIAG_WS = {}  # device index -> workspace (summary + per-workgroup partials)
+
+
+class DiagResult(dict):
+    """chain_diag's result: the requested output tensors by name and
+    `summary`, read lazily — the first access copies the struct from the
+    device (one D2H copy, one sync of the launch stream) and is cached."""
+
+    def __init__(self, outs, ws, event, thresholds):
+        super().__init__(outs)
+        self._ws, self._event, self._thresholds, self._summary = ws, event, thresholds, None
+
+    def __missing__(self, key):
+        if key != "summary":
+            raise KeyError(key)
+        return self.summary
+
+    @property
+    def summary(self):
+        if self._summary is None:
+            self._event.synchronize()
+            raw = self._ws.cpu().numpy().tobytes()
+            s = L.DiagSummary.from_buffer_copy(raw)
+            ne = int(s.n_eval)
+            above = [int(v) for v in s.n_above]
+            self._summary = {
+                "n_eval": ne, "n_degenerate": int(s.n_degenerate),
+                "n_nonfinite": int(s.n_nonfinite), "argmax": int(s.argmax), "n_above": above,
+                "rhat_sum": float(s.rhat_sum), "rhat_max": float(s.rhat_max),
+                "rhat_mean": float(s.rhat_sum) / ne if ne else float("nan"),
+                "share_above": [v / ne if ne else float("nan") for v in above],
+                "thresholds": list(self._thresholds)}
+            self._ws = None
+        return self._summary
+
+
+def chain_diag(mom1, mom2, *, chains, chain_groups, n, var_mode, ratio, count, var_floor=1e-12,
+               thresholds=(1.01, 1.05, 1.1), want=("rhat",), blocks_per_cu=0, div_mode=None):
+    """Cross-chain R-hat and pooled posterior of `chains` stacked chains
+    (bdl_chain_diag, include/bdl_diag.h): chain k's element j at
+    4*chain_groups*k + j of mom1 / mom2, n elements per chain evaluated,
+    (var_mode, ratio) as the posterior draw's, count = samples collected per
+    chain.  want: any of DIAG_OUTPUTS — each an [n] tensor in the result;
+    result["summary"] is read on first access.  One sweep and a one-workgroup
+    combine on the current stream, no host synchronisation here.  Values never
+    depend on blocks_per_cu (1-8, 0: default)."""
+    if mom2 is None:
+        raise ValueError("chain_diag: the second moment is required (mom2 is None)")
+    if mom1 is None:
+        raise ValueError("chain_diag: mom1 is required")
+    L.require_hip(mom1, "mom1")
+    L.require_hip(mom2, "mom2")
+    if int(count) < 2:
+        raise ValueError(f"chain_diag: R-hat needs at least 2 samples per chain (count = {count})")
+    chains, chain_groups, n = int(chains), int(chain_groups), int(n)
+    if chains < 2:
+        raise ValueError(f"chain_diag: at least 2 chains are required (chains = {chains})")
+    if not 1 <= n <= 4 * chain_groups:
+        raise ValueError("chain_diag: 1 <= n <= 4 * chain_groups is required")
+    need = 4 * chain_groups * (chains - 1) + n
+    for nm, t in (("mom1", mom1), ("mom2", mom2)):
+        if not t.is_contiguous() or t.numel() < need:
+            raise ValueError(f"chain_diag: {nm} must be contiguous with at least {need} elements")
+    if mom2.device != mom1.device:
+        raise ValueError("chain_diag: mom1 and mom2 must be on one device")
+    want = tuple(want)
+    if len(thresholds) != 3 or any(w not in DIAG_OUTPUTS for w in want):
+        raise ValueError(f"chain_diag: three thresholds, and want from {DIAG_OUTPUTS}")
+    dev = mom1.device
+    ws = _DIAG_WS.get(dev.index)
+    if ws is None:
+        nbytes = int(L.lib().bdl_chain_diag_workspace_bytes(n))
+        ws = _DIAG_WS[dev.index] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    outs = {w: torch.empty(n, dtype=torch.float32, device=dev) for w in want}
+    a = L.DiagArgs()
+    a.mom1, a.mom2 = mom1.data_ptr(), mom2.data_ptr()
+    a.pooled_mean, a.pooled_var, a.rhat = (
+        outs[w].data_ptr() if w in outs else None for w in DIAG_OUTPUTS)
+    a.workspace = ws.data_ptr()
+    a.n, a.chain_groups, a.chains = n, chain_groups, chains
+    a.var_mode = int(var_mode)
+    a.ratio = float(ratio)
+    # WELFORD M2 / (n-1): torch-on-GPU multiplies by the reciprocal (as posterior_sample)
+    a.inv_ratio = _inv(ratio) if _div_flag(div_mode) else 0.0
+    a.var_floor = float(var_floor)
+    a.c1 = (int(count) - 1) / int(count)
+    for i, t in enumerate(thresholds):
+        a.thresholds[i] = float(t)
+    a.blocks_per_cu = int(blocks_per_cu)
+    L.check(L.lib().bdl_chain_diag(a, L.current_stream_handle(dev)), "bdl_chain_diag")
+    # the struct leaves the shared workspace in stream order, so a later call
+    # on this device cannot overwrite a summary that was not read yet
+    snap = ws[:C.sizeof(L.DiagSummary)].clone()
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(dev))
+    return DiagResult(outs, snap, ev, thresholds)
 
 
 def philox_normal(n, seed, chain, step, device="cuda"):

@@ -108,6 +108,9 @@ def build_parser():
     ap.add_argument("--stacked_chains", type=int, default=0,
                     help="csghmc / sghmc / sgld / csgld: K > 0 chains per device stepped together "
                          "(bayesdll_amd.stacked; no BatchNorm statistics)")
+    ap.add_argument("--rhat", action="store_true",
+                    help="with --stacked_chains >= 2: log the cross-chain R-hat of the collected "
+                         "moments at every evaluation (stacked diagnostics())")
     return ap
 
 
@@ -147,7 +150,10 @@ def prepare(args, device):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.rhat and args.stacked_chains < 2:
+        ap.error("--rhat compares the chains of one device: it needs --stacked_chains >= 2")
     from . import chains
     rank, world, device = chains.init_chains()
     if device.type != "cuda":

@@ -396,6 +396,60 @@ class _StackedSampler:
                            chain_groups=self.state.chain_groups)
         self.draws += 1
 
+    # ---------------------------------------------------------- diagnostics
+    def _latest_component(self):
+        """The component collected last (None while nothing is collected)."""
+        raise NotImplementedError
+
+    def _moment_spec(self, component):
+        """(m1, m2, var_mode, ratio, count) of a collected component: the K
+        chains' stacked moments, the very (var_mode, ratio) `_components`
+        draws from them with, and the number of collects into them (m1 None:
+        not collected; m2 None: the second moment is not kept / not used)."""
+        raise NotImplementedError
+
+    def param_of(self, index):
+        """Name of the parameter tensor holding flat element `index` of a chain."""
+        st = self.state
+        i = int(np.searchsorted(np.asarray(st.offsets), int(index), side="right")) - 1
+        return st.names[max(i, 0)]
+
+    def diagnostics(self, component=None, *, rhat=False, pooled=False):
+        """Do the K chains agree?  The cross-chain Gelman-Rubin R-hat and the
+        pooled Gaussian posterior of a collected component (default: the
+        latest), from the chains' moments in one fused sweep
+        (kernels.chain_diag).  Returns the summary (n_eval, n_degenerate,
+        n_nonfinite, rhat_max, argmax and its parameter name, rhat_mean,
+        n_above / share_above the thresholds 1.01 / 1.05 / 1.1, count,
+        component) plus, when asked for, the [n1] tensors `rhat` and
+        `pooled_mean` / `pooled_var`.  Reads the moments only: nothing the
+        sampler owns is written."""
+        if self.K < 2:
+            raise ValueError("diagnostics: R-hat compares chains; this sampler runs K = 1")
+        if component is None:
+            component = self._latest_component()
+        m1 = None
+        if component is not None:
+            m1, m2, var_mode, ratio, count = self._moment_spec(component)
+        if m1 is None:
+            raise ValueError("diagnostics: nothing is collected yet"
+                             + ("" if component is None else f" for component {component!r}"))
+        if count < 2:
+            raise ValueError(f"diagnostics: component {component!r} holds {count} sample per "
+                             "chain; the within-chain variance needs at least 2")
+        if m2 is None:
+            raise ValueError("diagnostics: the second moment is not kept (nst = 0), so there is "
+                             "no within-chain variance")
+        st = self.state
+        want = (("rhat",) if rhat else ()) + (("pooled_mean", "pooled_var") if pooled else ())
+        res = K.chain_diag(m1, m2, chains=self.K, chain_groups=st.chain_groups, n=st.n1,
+                           var_mode=var_mode, ratio=ratio, count=count, want=want)
+        out = dict(res.summary)
+        out["component"], out["count"] = component, int(count)
+        out["argmax_param"] = self.param_of(out["argmax"]) if out["argmax"] >= 0 else None
+        out.update({w: res[w] for w in want})
+        return out
+
     def evaluate(self, loader):
         """(NLL, error) of the stacked predictive over a data loader (the
         network in eval mode, as the reference's evaluate)."""
@@ -468,8 +522,26 @@ class _StackedSampler:
                 rec["test"] = self.evaluate(test_loader)
                 log(f"(Epoch {ep}) stacked predictive: loss = {rec['test'][0]:.4f}, "
                     f"error = {rec['test'][1]:.4f}")
+                if getattr(self.args, "rhat", False):  # opt-in (run.py --rhat)
+                    self._report_rhat(ep, rec, log)
             hist.append(rec)
         return hist
+
+    def _report_rhat(self, ep, rec, log):
+        """One log line and rec["rhat"] from `diagnostics()`; an evaluation
+        that comes before the diagnostic is defined says so and goes on."""
+        try:
+            d = self.diagnostics()
+        except ValueError as e:
+            log(f"(Epoch {ep}) R-hat: {e}")
+            return
+        rec["rhat"] = d
+        shares = ", ".join(f"> {t:g}: {100 * s:.1f} %"
+                           for t, s in zip(d["thresholds"], d["share_above"]))
+        log(f"(Epoch {ep}) R-hat over {self.K} chains, component {d['component']} "
+            f"({d['count']} samples each): max = {d['rhat_max']:.4f} ({d['argmax_param']}), "
+            f"mean = {d['rhat_mean']:.4f}, {shares}; {d['n_eval']} evaluated, "
+            f"{d['n_degenerate']} degenerate, {d['n_nonfinite']} non-finite")
 
 
 class StackedCSGHMC(_StackedSampler):
@@ -547,15 +619,27 @@ class StackedCSGHMC(_StackedSampler):
         variance M2/(n-1), 1e-12 for a single sample; methods/csghmc.py:446-468)
         or, with nst = 0, its mean."""
         for c in sorted(self.mom1):
-            n = self.samples_per_cycle.get(c, 0)
+            m1, m2, var_mode, ratio, _ = self._moment_spec(c)
             for _ in range(max(1, self.nst)):
                 if self.nst == 0:
-                    buf.copy_(self.mom1[c])
-                elif n > 1:
-                    self._sample(buf, self.mom1[c], self.mom2[c], L.VAR_WELFORD, float(n - 1))
+                    buf.copy_(m1)
                 else:
-                    self._sample(buf, self.mom1[c], None, L.VAR_GIVEN, 1.0)
+                    self._sample(buf, m1, m2, var_mode, ratio)
                 yield c
+
+    def _latest_component(self):
+        return max(self.mom1) if self.mom1 else None
+
+    def _moment_spec(self, c):
+        """Cycle c: Welford mean and M2 / (n - 1) with n the stored count —
+        doubled by quirk Q2, so the cycle holds n // 2 collects per chain (a
+        count of 1 or less draws with the variance floor alone, no M2)."""
+        if c not in self.mom1:
+            return None, None, L.VAR_GIVEN, 1.0, 0
+        n = self.samples_per_cycle.get(c, 0)
+        if n > 1:
+            return self.mom1[c], self.mom2[c], L.VAR_WELFORD, float(n - 1), n // 2
+        return self.mom1[c], None, L.VAR_GIVEN, 1.0, n // 2
 
     def _evaluate_after(self, ep, loader):
         return self.sched.last_in_cycle(epoch=ep, batch=len(loader) - 1,
@@ -661,13 +745,24 @@ class StackedSGLD(_StackedSampler):
         sample; methods/sgld.py:324-350), or the posterior mean (nst = 0)."""
         if self.m1 is None:
             return
+        m1, m2, var_mode, ratio, _ = self._moment_spec(0)
         for _ in range(max(1, self.nst)):
             if self.nst == 0:
-                buf.copy_(self.m1)
+                buf.copy_(m1)
             else:
-                ratio = self.cnt / (self.cnt - 1) if self.cnt > 1 else 1.0
-                self._sample(buf, self.m1, self.m2, L.VAR_RAW_MOMENTS, ratio)
+                self._sample(buf, m1, m2, var_mode, ratio)
             yield 0
+
+    def _latest_component(self):
+        return None if self.m1 is None else 0
+
+    def _moment_spec(self, component=0):
+        """The one component: running (m1, m2) over cnt collects, the burn-in
+        seed included; var = cnt/(cnt-1) * (m2 - m1^2), ratio 1 for one sample."""
+        if self.m1 is None or component != 0:
+            return None, None, L.VAR_RAW_MOMENTS, 1.0, 0
+        ratio = self.cnt / (self.cnt - 1) if self.cnt > 1 else 1.0
+        return self.m1, self.m2, L.VAR_RAW_MOMENTS, ratio, self.cnt
 
     def _evaluate_after(self, ep, loader):
         freq = int(getattr(self.args, "test_eval_freq", 1) or 1)
@@ -729,14 +824,25 @@ class StackedCSGLD(StackedSGLD):
         """Every collected cycle: nst draws with var = spc/(spc-1) * (m2 - m1^2)
         (ratio 1 for a one-sample cycle; methods/csgld.py:394-400), or its mean."""
         for c in sorted(self.mom1):
-            spc = self.samples_per_cycle.get(c, 0)
+            m1, m2, var_mode, ratio, _ = self._moment_spec(c)
             for _ in range(max(1, self.nst)):
                 if self.nst == 0:
-                    buf.copy_(self.mom1[c])
+                    buf.copy_(m1)
                 else:
-                    self._sample(buf, self.mom1[c], self.mom2[c], L.VAR_RAW_MOMENTS,
-                                 spc / (spc - 1) if spc > 1 else 1.0)
+                    self._sample(buf, m1, m2, var_mode, ratio)
                 yield c
+
+    def _latest_component(self):
+        return max(self.mom1) if self.mom1 else None
+
+    def _moment_spec(self, c):
+        """Cycle c: running (m1, m2) over its spc collects; var = spc/(spc-1) *
+        (m2 - m1^2), ratio 1 for a one-sample cycle."""
+        if c not in self.mom1:
+            return None, None, L.VAR_RAW_MOMENTS, 1.0, 0
+        spc = self.samples_per_cycle.get(c, 0)
+        return (self.mom1[c], self.mom2[c], L.VAR_RAW_MOMENTS,
+                spc / (spc - 1) if spc > 1 else 1.0, spc)
 
     def _evaluate_after(self, ep, loader):
         return self.sched.last_in_cycle(epoch=ep, batch=len(loader) - 1,
