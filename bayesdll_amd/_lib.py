@@ -140,6 +140,26 @@ DIAG_EXPORTS = {
     "bdl_chain_diag": (C.c_int, [C.POINTER(DiagArgs), C.c_void_p]),
 }
 
+
+class ClipSegment(C.Structure):
+    """include/bdl_clip.h bdl_clip_segment (a row of the device table: three int64)."""
+    _fields_ = [("base", _fp), ("numel", C.c_int64), ("chain_stride", C.c_int64)]
+
+
+class ClipArgs(C.Structure):
+    """include/bdl_clip.h bdl_chain_clip_args."""
+    _fields_ = [("segments", _fp), ("nsegments", C.c_int32), ("chains", C.c_int32),
+                ("max_norm", C.c_float), ("blocks_per_chain", C.c_int32), ("workspace", _fp)]
+
+
+CLIP_MAX_SEGMENTS, CLIP_MAX_CHAINS, CLIP_MAX_BLOCKS_PER_CHAIN = 65536, 65535, 1024
+
+# include/bdl_clip.h: additive to the ABI, as DIAG_EXPORTS
+CLIP_EXPORTS = {
+    "bdl_chain_clip_workspace_bytes": (C.c_int64, [C.c_int32]),
+    "bdl_chain_clip": (C.c_int, [C.POINTER(ClipArgs), C.c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -157,7 +177,8 @@ def lib():
                     "`make -C bayesdll_amd/csrc` (or __graft_entry__.build()). There is no CPU "
                     "fallback for the fused SG-MCMC step.")
             h = C.CDLL(LIB_PATH)
-            for name, (res, argt) in list(EXPORTS.items()) + list(DIAG_EXPORTS.items()):
+            for name, (res, argt) in (list(EXPORTS.items()) + list(DIAG_EXPORTS.items())
+                                      + list(CLIP_EXPORTS.items())):
                 fn = getattr(h, name)
                 fn.restype = res
                 fn.argtypes = argt

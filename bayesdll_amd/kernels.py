@@ -479,6 +479,72 @@ def chain_diag(mom1, mom2, *, chains, chain_groups, n, var_mode, ratio, count, v
     return DiagResult(outs, snap, ev, thresholds)
 
 
+_CLIP_WS = {}  # (device index, chains) -> workspace ((norm, coef) per chain + partials)
+
+
+def clip_bytes_per_elem(clipped_share=1.0):
+    """Algorithmic HBM bytes per gradient element of one chain_clip call
+    (DESIGN §4e): every element read once for the norm; the elements of the
+    clipped chains read and written once more."""
+    return 4 + 8 * float(clipped_share)
+
+
+def chain_clip_workspace(chains, device):
+    """A fresh workspace for chain_clip over `chains` chains (a float tensor
+    whose first 2 * chains elements are the (norm, coef) table)."""
+    nbytes = int(L.lib().bdl_chain_clip_workspace_bytes(int(chains)))
+    if nbytes <= 0:
+        raise ValueError(f"chain_clip: chains must be in [1, {L.CLIP_MAX_CHAINS}] (got {chains})")
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+
+
+def clip_blocks_per_chain(numel, chains, device=None):
+    """Workgroups per chain for a gradient of `numel` elements per chain: one
+    per 4096 elements (a full block iteration of the sweep), at most about four
+    per CU over all chains — a small network gets a small grid."""
+    cus = torch.cuda.get_device_properties(_device(device)).multi_processor_count
+    cap = max(1, -(-4 * cus // max(1, int(chains))))
+    return int(max(1, min(-(-int(numel) // 4096), cap, L.CLIP_MAX_BLOCKS_PER_CHAIN)))
+
+
+def chain_clip(segments, nsegments, chains, max_norm, workspace=None, blocks_per_chain=0):
+    """torch.nn.utils.clip_grad_norm_(max_norm) of every one of `chains`
+    stacked chains by the norm of its own gradient, in place on the device
+    (bdl_chain_clip, include/bdl_clip.h).  segments: the device table
+    (StackedState.grad_segments: an int64 [nsegments, 3] tensor of (base
+    address, numel, chain stride) rows).  Three launches on the current
+    stream, no host synchronisation.  Returns the [chains, 2] float view of
+    the workspace: (norm_k, coef_k) per chain.  workspace None: one cached per
+    device and chain count (the view is then overwritten by the next such
+    call).  Values do not depend on blocks_per_chain (0: the library's
+    default) beyond the fp64 summation order of the norm."""
+    if segments.dtype != torch.int64 or not segments.is_cuda or not segments.is_contiguous() \
+            or segments.numel() < 3 * int(nsegments):
+        raise ValueError("chain_clip: segments must be a contiguous int64 device tensor of "
+                         "nsegments x 3")
+    if not float(max_norm) > 0:
+        raise ValueError(f"chain_clip: max_norm must be > 0 (got {max_norm})")
+    chains, dev = int(chains), segments.device
+    if workspace is None:
+        workspace = _CLIP_WS.get((dev.index, chains))
+        if workspace is None:
+            workspace = _CLIP_WS[(dev.index, chains)] = chain_clip_workspace(chains, dev)
+    else:
+        L.require_hip(workspace, "workspace")
+        if workspace.device != dev or not workspace.is_contiguous() or \
+                4 * workspace.numel() < int(L.lib().bdl_chain_clip_workspace_bytes(chains)):
+            raise ValueError("chain_clip: workspace must be a contiguous float tensor of "
+                             "bdl_chain_clip_workspace_bytes(chains) bytes on the segments' device")
+    a = L.ClipArgs()
+    a.segments = segments.data_ptr()
+    a.nsegments, a.chains = int(nsegments), chains
+    a.max_norm = float(max_norm)
+    a.blocks_per_chain = int(blocks_per_chain)
+    a.workspace = workspace.data_ptr()
+    L.check(L.lib().bdl_chain_clip(a, L.current_stream_handle(dev)), "bdl_chain_clip")
+    return workspace[:2 * chains].view(chains, 2)
+
+
 def philox_normal(n, seed, chain, step, device="cuda"):
     """The N(0,1) values the step kernel draws in Philox mode, as a tensor."""
     out = torch.empty(n, dtype=torch.float32, device=device)

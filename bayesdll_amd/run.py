@@ -106,8 +106,9 @@ def build_parser():
     ap.add_argument("--resume_state", action="store_true",
                     help="checkpoints carry what an exact resume needs")
     ap.add_argument("--stacked_chains", type=int, default=0,
-                    help="csghmc / sghmc / sgld / csgld: K > 0 chains per device stepped together "
-                         "(bayesdll_amd.stacked; no BatchNorm statistics)")
+                    help="csghmc / sghmc / sgld / csgld / adam_sghmc / adam_csghmc: K > 0 chains "
+                         "per device stepped together (bayesdll_amd.stacked; no BatchNorm "
+                         "statistics; csgld and adam_csghmc honour --clip_grad per chain)")
     ap.add_argument("--rhat", action="store_true",
                     help="with --stacked_chains >= 2: log the cross-chain R-hat of the collected "
                          "moments at every evaluation (stacked diagnostics())")
@@ -208,9 +209,13 @@ def main(argv=None):
     if args.stacked_chains > 0:
         from . import stacked
         cls = {"csghmc": stacked.StackedCSGHMC, "sgld": stacked.StackedSGLD,
-               "csgld": stacked.StackedCSGLD, "sghmc": stacked.StackedSGHMC}.get(args.method)
+               "csgld": stacked.StackedCSGLD, "sghmc": stacked.StackedSGHMC,
+               "adam_sghmc": stacked.StackedAdamSGHMC,
+               "adam_csghmc": stacked.StackedAdamCSGHMC}.get(args.method)
         if cls is None:
-            raise ValueError("--stacked_chains: csghmc, sghmc, sgld or csgld")
+            raise ValueError(f"--stacked_chains: {args.method} is not stacked (csghmc, sghmc, "
+                             "sgld, csgld, adam_sghmc or adam_csghmc; csghmc_fs runs one chain "
+                             "per process)")
         S = cls(net, args.stacked_chains, args, logger=logger, init="reinit", graph=args.graph,
                 net0=net0)
         logger.info(f"{args.stacked_chains} stacked chains on this device "

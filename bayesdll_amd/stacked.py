@@ -25,8 +25,11 @@ run chain to rounding, not bitwise.
 Scope: StackedCSGHMC (the north-star sampler: cyclical schedule, thinning,
 per-cycle Welford moments), StackedSGLD (SGLD + SGD momentum, prior mean
 theta0, burn-in, thinned running moments), StackedSGHMC (the same loop with
-the SGHMC momentum update) and StackedCSGLD (cyclical SGLD, per-cycle running
-moments); the predictive averages
+the SGHMC momentum update), StackedCSGLD (cyclical SGLD, per-cycle running
+moments), StackedAdamSGHMC (Adam-preconditioned SGHMC under SGLD's loop) and
+StackedAdamCSGHMC (its cyclical variant, Adam state reset at every cycle end);
+the cyclical SGLD / Adam samplers honour args.clip_grad per chain, each chain by
+the norm of its own gradient (kernels.chain_clip).  The predictive averages
 probabilities uniformly over chains and (nst posterior draws of) the collected
 components.  Networks with BatchNorm running statistics are refused (vmap cannot
 update shared buffers per chain), and every trainable parameter must take part
@@ -132,6 +135,7 @@ class StackedState:
         gap = 1 if self.stride > self.n1 else 0
         self.grad_mode = "tensor" if self.K * (len(self.names) + gap) <= MAX_TENSOR_RUNS else "flat"
         self.grad, self.gbase, self._tables = None, None, {}
+        self._gbound, self._seg_tables = None, {}  # grad_segments: what use_grads bound last
         if self.grad_mode == "flat":
             self.grad2d = torch.zeros(self.K, self.stride, **f32)
             self.grad = self.grad2d.view(-1)
@@ -166,6 +170,7 @@ class StackedState:
             for g, o, k in zip(gl, self.offsets, self.numels):
                 if g is not None:
                     self.grad2d[:, o:o + k].copy_(g.reshape(self.K, k))
+            self._gbound = tuple(g is not None for g in gl)
             return
         ptrs = []
         for g, k in zip(gl, self.numels):
@@ -176,7 +181,7 @@ class StackedState:
                     or g.numel() != self.K * k):
                 raise ValueError("StackedState: gradients must be contiguous fp32 [K, *shape]")
             ptrs.append(g.data_ptr())
-        key = tuple(ptrs)
+        key = self._gbound = tuple(ptrs)
         tab = self._tables.get(key)
         if tab is None:
             tab = self._build_table(ptrs)
@@ -210,6 +215,34 @@ class StackedState:
         dev = host.to(self.device, non_blocking=True)
         return dev[:2 * nt].view(nt, 2), nt, dev[2 * nt:]
 
+    def grad_segments(self):
+        """(device table, nsegments) of kernels.chain_clip for the gradients
+        `use_grads` last bound: one (base address, numel, chain stride) row per
+        tensor that has a gradient (include/bdl_clip.h) — the vmapped
+        [K, *shape] tensor itself ("tensor" mode: stride = numel) or its span
+        of the stacked gradient vector ("flat": stride = the chain slot).  A
+        frozen tensor / a missing gradient gets no row, a chain's padding lies
+        in none.  Cached per set of gradient addresses, as the run tables."""
+        key = self._gbound
+        if key is None:
+            raise ValueError("StackedState: grad_segments before use_grads")
+        tab = self._seg_tables.get(key)
+        if tab is None:
+            if self.grad_mode == "flat":
+                rows = [(self.grad.data_ptr() + 4 * o, n, self.stride)
+                        for o, n, have in zip(self.offsets, self.numels, key) if have]
+            else:
+                rows = [(ptr, n, n) for n, ptr in zip(self.numels, key) if ptr]
+            if not rows:
+                raise ValueError("StackedState: no tensor has a gradient to clip")
+            host = torch.empty(len(rows), 3, dtype=torch.int64).pin_memory()
+            host.numpy()[:] = np.asarray(rows, dtype=np.int64)
+            tab = (host.to(self.device, non_blocking=True), len(rows))
+            if len(self._seg_tables) >= 8:
+                self._seg_tables.pop(next(iter(self._seg_tables)))
+            self._seg_tables[key] = tab
+        return tab
+
     def diverged(self, reset=True):
         bad = bool(self.nonfinite.item())
         if bad and reset:
@@ -229,6 +262,12 @@ class _StackedSampler:
 
     need_prior = False
     tune_method = "csghmc"  # the production kernel autotune_once times
+    # per-chain clip_grad_norm_ threshold (the cyclical SGLD / Adam samplers set
+    # it from args.clip_grad) and the [K, 2] (norm, coef) device table of the
+    # last clipped step
+    clip_grad = None
+    last_clip = None
+    _clip_ws = None
 
     def __init__(self, net, K_, args, *, chain0=None, seed=None, init="copy", criterion=None,
                  per_chain_batches=False, logger=None, graph=None, net0=None):
@@ -341,6 +380,20 @@ class _StackedSampler:
         grads, loss, out = self.gradients(x, y)
         self.update(grads, *a, **kw)
         return loss, out
+
+    def _clip_chains(self):
+        """clip_grad_norm_(self.clip_grad) of every chain by the norm of its
+        own sampler gradient — K stacked chains stand for K Runners, each
+        clipping its own (methods/csgld.py:250-253, adam_csghmc.py:319-322) —
+        in place in the gradients `use_grads` bound (kernels.chain_clip: three
+        launches, no sync).  Keeps the (norm, coef) table in `last_clip`."""
+        st = self.state
+        seg, nseg = st.grad_segments()
+        if self._clip_ws is None:
+            self._clip_ws = K.chain_clip_workspace(self.K, st.device)
+            self._clip_bpc = K.clip_blocks_per_chain(st.n1, self.K, st.device)
+        self.last_clip = K.chain_clip(seg, nseg, self.K, self.clip_grad, workspace=self._clip_ws,
+                                      blocks_per_chain=self._clip_bpc)
 
     def _accumulate(self, acc, loss, out, y):
         """Per-chain running (loss sum, error count, examples) on the device."""
@@ -518,6 +571,13 @@ class _StackedSampler:
             log(f"[Epoch {ep}/{self.args.epochs}] {self.K} chains: loss = {lt.mean():.4f} "
                 f"(min {lt.min():.4f}, max {lt.max():.4f}), error = {et.mean():.4f} "
                 f"({rec['seconds']:.2f} s)")
+            if self.clip_grad is not None and self.last_clip is not None:
+                # (the epoch's sync is behind us: train_one_epoch read its losses)
+                lc = self.last_clip.cpu().numpy()
+                rec["clip"] = {"clipped": int((lc[:, 1] < 1).sum()), "max_norm": float(lc[:, 0].max())}
+                log(f"[Epoch {ep}] clip_grad {self.clip_grad:g}: {rec['clip']['clipped']} of "
+                    f"{self.K} chains clipped at the last step, largest gradient norm = "
+                    f"{rec['clip']['max_norm']:.4g}")
             if test_loader is not None and self._evaluate_after(ep, train_loader):
                 rec["test"] = self.evaluate(test_loader)
                 log(f"(Epoch {ep}) stacked predictive: loss = {rec['test'][0]:.4f}, "
@@ -702,11 +762,22 @@ class StackedSGLD(_StackedSampler):
         mom = self.mu != 0
         ckind, m1, m2, ca, cb = (L.COLLECT_NONE, None, None, 1.0, 1.0) if collect is None \
             else collect
-        K.sgmcmc_step(st, L.SGLD, lrs=lrs, noise_scale=ns, noise_mode=L.NOISE_PHILOX,
-                      prior_sig=self.prior_sig, sigma2=self.prior_sig ** 2, n_data=N, mu=self.mu,
-                      first_step=mom and not self.has_buffer, momentum=mom, collect=ckind,
-                      mom1=m1, mom2=m2, collect_a=ca, collect_b=cb, seed=self.seed,
-                      chain=self.chain0, step=self.step_count)
+        key = dict(seed=self.seed, chain=self.chain0, step=self.step_count)
+        sgd_kw = dict(mu=self.mu, first_step=mom and not self.has_buffer, momentum=mom,
+                      collect=ckind, mom1=m1, mom2=m2, collect_a=ca, collect_b=cb)
+        if self.clip_grad is not None:
+            # methods/csgld.py:250-253: clip_grad_norm_ on p.grad between
+            # Model.forward and optimizer.step, per chain: the sampler gradient
+            # in place, each chain's own norm and scale, then SGD's step alone
+            K.sgmcmc_step(st, L.SGLD_GRAD, lrs=lrs, noise_scale=ns, noise_mode=L.NOISE_PHILOX,
+                          prior_sig=self.prior_sig, sigma2=self.prior_sig ** 2, n_data=N, **key)
+            self._clip_chains()
+            K.sgmcmc_step(st, L.SGLD, lrs=lrs, noise_scale=(0.0, 0.0), noise_mode=L.NOISE_NONE,
+                          sigma2=1.0, n_data=1.0, grad_ready=True, **sgd_kw, **key)
+        else:
+            K.sgmcmc_step(st, L.SGLD, lrs=lrs, noise_scale=ns, noise_mode=L.NOISE_PHILOX,
+                          prior_sig=self.prior_sig, sigma2=self.prior_sig ** 2, n_data=N,
+                          **sgd_kw, **key)
         self.has_buffer = self.has_buffer or mom
         self.step_count += 1
 
@@ -781,11 +852,17 @@ class StackedCSGLD(StackedSGLD):
     """K cyclical-SGLD chains (methods/csgld.py:195-331 per chain): SGLD + SGD
     momentum under the cyclical step size, per-cycle running moments
     (m1 = theta, m2 = theta^2 at a cycle's first sample, then the running
-    mean) on the sample steps.  No burn-in; `args` as the csgld Runner's."""
+    mean) on the sample steps.  No burn-in; `args` as the csgld Runner's,
+    args.clip_grad included (:250-253): every chain is clipped by the norm of
+    its own sampler gradient (`_clip_chains`)."""
 
     def __init__(self, net, K_, args, **kw):
         super().__init__(net, K_, args, **kw)
         self.burnin = -1  # cSGLD collects per cycle, not after a burn-in
+        clip = getattr(args, "clip_grad", None)
+        if clip is not None and not float(clip) > 0:
+            raise ValueError(f"clip_grad must be > 0 (got {clip})")
+        self.clip_grad = None if clip is None else float(clip)
         self.sched = CyclicalSGMCMC(base_lr=args.lr, nbr_of_cycles=getattr(args, "num_cycles", 10),
                                     epochs=args.epochs,
                                     proportion_exploration=getattr(args, "proportion_exploration",
@@ -817,8 +894,14 @@ class StackedCSGLD(StackedSGLD):
             loss, out = self.step(x, y, (lr, lr * (args.lr_head / args.lr)), collect=spec)
             if ss:
                 self.samples_per_cycle[c] = self.samples_per_cycle.get(c, 0) + 1
+            if sched.last_in_cycle(epoch=epoch, batch=b, batches_per_epoch=bpe):
+                self._cycle_end()
             self._accumulate(acc, loss, out, y)
         return self._epoch_result(acc)
+
+    def _cycle_end(self):
+        """Hook at every last_in_cycle step, after the step and its collect
+        (bayesdll_amd.csgld.Runner._cycle_end)."""
 
     def _components(self, buf):
         """Every collected cycle: nst draws with var = spc/(spc-1) * (m2 - m1^2)
@@ -884,3 +967,128 @@ class StackedSGHMC(StackedSGLD):
                       collect_a=ca, collect_b=cb, seed=self.seed, chain=self.chain0,
                       step=self.step_count)
         self.step_count += 1
+
+
+class _AdamStep:
+    """The Adam-preconditioned SGHMC step of K stacked chains
+    (bayesdll_amd.adam_sghmc.Model.forward's `sgd is not None` branch, per
+    chain): v_mom in the state's momentum vector, the stacked adam_m / adam_v /
+    sgd_buf in `state.extra` (kernels.ADAM_EXTRA), one step counter t for all
+    chains — they step together —, incremented before the launch.  Mixed into
+    the SGLD / cSGLD stacked samplers, whose loops, moments and evaluation
+    stay as they are."""
+
+    tune_method = "adam"
+    grad_is_mom = False  # the cyclical variant's p.grad = v_mom (adam_csghmc.py:834)
+
+    def _init_adam(self):
+        hp, st = self.args.hparams, self.state
+        self.momentum_decay = float(hp["momentum_decay"])
+        self.beta1 = float(hp.get("beta1", 0.9))
+        self.beta2 = float(hp.get("beta2", 0.999))
+        self.epsilon = float(hp.get("epsilon", 1e-8))
+        self.temperature = float(hp.get("temperature", 1.0))
+        self.t = 0
+        for nm in K.ADAM_EXTRA[:2]:
+            st.extra[nm] = torch.zeros_like(st.theta)
+
+    def _sgd_buffer(self):
+        """The stacked torch.optim.SGD momentum buffer (allocated when SGD
+        momentum is in use: adam_sghmc.Model.ensure_sgd_buffer)."""
+        ex = self.state.extra
+        if "sgd_buf" not in ex:
+            ex["sgd_buf"] = torch.zeros_like(self.state.theta)
+        return ex["sgd_buf"]
+
+    def update(self, grads, lrs, collect=None):
+        """One fused Adam-SGHMC + SGD launch over all chains
+        (methods/adam_sghmc.py:500-553 + :229), optional running-moment
+        collect; with clip_grad, adam_sghmc.Model.forward's clip branch: the
+        ADAM_SGHMC_GRAD launch, every chain's own clip, SGD's step."""
+        args, st = self.args, self.state
+        st.use_grads(grads)
+        self.t += 1
+        N = args.ND * self.Ninflate
+        key = dict(seed=self.seed, chain=self.chain0, step=self.step_count)
+        common = dict(adam_m=st.extra["adam_m"], adam_v=st.extra["adam_v"], beta1=self.beta1,
+                      beta2=self.beta2, eps=self.epsilon, t=self.t,
+                      momentum_decay=self.momentum_decay, nd=self.nd,
+                      temperature=self.temperature, grad_is_mom=self.grad_is_mom, lrs=lrs,
+                      noise_mode=L.NOISE_PHILOX, sigma2=self.prior_sig ** 2, n_data=N, **key)
+        ckind, m1, m2, ca, cb = (L.COLLECT_NONE, None, None, 1.0, 1.0) if collect is None \
+            else collect
+        mom = self.mu != 0
+        buf = self._sgd_buffer() if mom else None
+        sgd_kw = dict(mu=self.mu, first_step=mom and not self.has_buffer, momentum=mom,
+                      collect=ckind, mom1=m1, mom2=m2, collect_a=ca, collect_b=cb)
+        if self.clip_grad is not None:
+            # adam_csghmc.py:319-322: clip_grad_norm_ on p.grad between
+            # Model.forward and optimizer.step, per chain
+            K.adam_step(st, L.ADAM_SGHMC_GRAD, **common)
+            self._clip_chains()
+            K.sgmcmc_step(st, L.SGLD, lrs=lrs, noise_scale=(0.0, 0.0), noise_mode=L.NOISE_NONE,
+                          sigma2=1.0, n_data=1.0, grad_ready=True, mom_buf=buf, **sgd_kw, **key)
+        else:
+            K.adam_step(st, L.ADAM_SGHMC, sgd_buf=buf, **common, **sgd_kw)
+        self.has_buffer = self.has_buffer or mom
+        self.step_count += 1
+
+    def reset_adam(self):
+        """Zero v_mom, m, v and t (adam_sghmc.Model.reset_adam;
+        methods/adam_csghmc.py:372-378, :119-131)."""
+        st = self.state
+        st.mom.zero_()
+        st.extra["adam_m"].zero_()
+        st.extra["adam_v"].zero_()
+        self.t = 0
+
+    def _extra_state(self):
+        ex = self.state.extra
+        return dict(super()._extra_state(), adam_m=ex["adam_m"], adam_v=ex["adam_v"],
+                    sgd_buf=ex.get("sgd_buf"), t=self.t, has_buffer=self.has_buffer)
+
+    def _load_extra_state(self, d):
+        super()._load_extra_state(d)
+        ex = self.state.extra
+        with torch.no_grad():
+            ex["adam_m"].copy_(d["adam_m"])
+            ex["adam_v"].copy_(d["adam_v"])
+            if d["sgd_buf"] is not None:
+                self._sgd_buffer().copy_(d["sgd_buf"])
+        self.t, self.has_buffer = int(d["t"]), bool(d["has_buffer"])
+
+
+class StackedAdamSGHMC(_AdamStep, StackedSGLD):
+    """K Adam-preconditioned SGHMC chains (methods/adam_sghmc.py:16-556 per
+    chain; bayesdll_amd.adam_sghmc): the Adam-SGHMC momentum update and
+    SGD(momentum=args.momentum) in one fused launch for all chains, under the
+    SGLD Runner's burn-in / thinned running moments.  `args` as the adam_sghmc
+    Runner's (hparams with momentum_decay, beta1, beta2, epsilon,
+    temperature).  No clipping: the reference's Runner has none."""
+
+    def __init__(self, net, K_, args, **kw):
+        super().__init__(net, K_, args, **kw)
+        self._init_adam()
+
+
+class StackedAdamCSGHMC(_AdamStep, StackedCSGLD):
+    """K cyclical Adam-SGHMC chains (methods/adam_csghmc.py:17-863 per chain;
+    bayesdll_amd.adam_csghmc): grad_U = g / temperature + prior pull,
+    p.grad = v_mom, SGD momentum forced to 0 (:70), the cyclical step size and
+    csgld's per-cycle running moments; v_mom, m, v and t zeroed at every
+    last_in_cycle step (:372-378); args.clip_grad clips every chain by its own
+    norm (:319-322).  Cold restarts (perform_cold_restarts: a per-chain
+    re-initialisation mid-run) are not stacked."""
+
+    grad_is_mom = True
+
+    def __init__(self, net, K_, args, **kw):
+        if str(args.hparams.get("perform_cold_restarts", False)).lower() == "true":
+            raise ValueError("StackedAdamCSGHMC: perform_cold_restarts=true is not supported by "
+                             "stacked chains (run one chain per process for cold restarts)")
+        super().__init__(net, K_, args, **kw)
+        self._init_adam()
+        self.mu = 0.0  # :70 "Force SGD optimizer momentum to 0"
+
+    def _cycle_end(self):
+        self.reset_adam()
