@@ -160,6 +160,44 @@ CLIP_EXPORTS = {
     "bdl_chain_clip": (C.c_int, [C.POINTER(ClipArgs), C.c_void_p]),
 }
 
+
+
+class ChainScalars(C.Structure):
+    """include/bdl_chain_step.h bdl_chain_scalars (a row of the device table: 12 floats)."""
+    _fields_ = [("lr", C.c_float * 2), ("noise_scale", C.c_float * 2),
+                ("one_minus_alpha", C.c_float), ("prior_sig", C.c_float), ("sigma2", C.c_float),
+                ("n_data", C.c_float), ("mu", C.c_float), ("inv_sigma2", C.c_float),
+                ("inv_n_data", C.c_float), ("pad", C.c_float)]
+
+
+class ChainStepArgs(C.Structure):
+    """include/bdl_chain_step.h bdl_chain_step_args."""
+    _fields_ = [
+        ("theta", _fp), ("grad", _fp), ("mom", _fp), ("prior_mean", _fp), ("noise", _fp),
+        ("mom1", _fp), ("mom2", _fp), ("nonfinite", _fp), ("runs", _fp), ("grad_base", _fp),
+        ("scalars", _fp), ("n1", C.c_int64), ("chain_groups", C.c_uint64),
+        ("nruns", C.c_int32), ("chains", C.c_int32), ("method", C.c_int32),
+        ("noise_mode", C.c_int32), ("collect", C.c_int32), ("flags", C.c_int32),
+        ("blocks_per_chain", C.c_int32), ("unroll", C.c_int32),
+        ("nonfinite_per_chain", C.c_int32), ("pad0", C.c_int32),
+        ("collect_a", C.c_float), ("collect_b", C.c_float), ("inv_collect_a", C.c_float),
+        ("inv_collect_b", C.c_float),
+        ("seed", C.c_uint64), ("chain", C.c_uint64), ("step", C.c_uint64),
+    ]
+
+
+# the columns of a scalar row, in bdl_chain_scalars order
+CHAIN_SCALAR_COLUMNS = ("lr0", "lr1", "ns0", "ns1", "one_minus_alpha", "prior_sig", "sigma2",
+                        "n_data", "mu", "inv_sigma2", "inv_n_data", "pad")
+CHAIN_STEP_MAX_CHAINS, CHAIN_STEP_MAX_BLOCKS_PER_CHAIN = 65535, 4096
+CHAIN_STEP_MAX_RUNS, CHAIN_STEP_MAX_RUNS_BASES = 4096, 2730
+
+# include/bdl_chain_step.h: additive to the ABI, as DIAG_EXPORTS
+CHAIN_STEP_EXPORTS = {
+    "bdl_chain_step_unroll_ok": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "bdl_chain_step": (C.c_int, [C.POINTER(ChainStepArgs), C.c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -178,7 +216,8 @@ def lib():
                     "fallback for the fused SG-MCMC step.")
             h = C.CDLL(LIB_PATH)
             for name, (res, argt) in (list(EXPORTS.items()) + list(DIAG_EXPORTS.items())
-                                      + list(CLIP_EXPORTS.items())):
+                                      + list(CLIP_EXPORTS.items())
+                                      + list(CHAIN_STEP_EXPORTS.items())):
                 fn = getattr(h, name)
                 fn.restype = res
                 fn.argtypes = argt

@@ -32,6 +32,12 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1
 #ifdef BDL_PHILOX_KEYS_PER_CALL
   asm volatile("" : "+s"(k0), "+s"(k1));
 #endif
+  // BDL_PHILOX_ROUND_KEYS_PER_CALL: the same for the round keys alone, the
+  // generator's inputs staying where the caller's argument view holds them
+  // (bdl_chain_step.hip, whose workgroups build their arguments in registers)
+#if defined(BDL_PHILOX_ROUND_KEYS_PER_CALL) && !defined(BDL_PHILOX_KEYS_PER_CALL)
+  asm volatile("" : "+s"(k0), "+s"(k1));
+#endif
 #pragma unroll
   for (int i = 0; i < 10; ++i) {
     const uint64_t p0 = (uint64_t)0xD2511F53u * c.x;

@@ -545,6 +545,93 @@ def chain_clip(segments, nsegments, chains, max_norm, workspace=None, blocks_per
     return workspace[:2 * chains].view(chains, 2)
 
 
+CHAIN_STEP_WG_PER_CU = 2  # default grid of chain_step: about this many workgroups per CU
+
+
+def chain_step_blocks_per_chain(n1, chains, device=None, unroll=1):
+    """Workgroups per chain for chain_step over `n1` elements per chain: about
+    CHAIN_STEP_WG_PER_CU per CU over all chains, never more than the chain has
+    block iterations (256 * unroll float4 groups each)."""
+    cus = torch.cuda.get_device_properties(_device(device)).multi_processor_count
+    iters = -(-((int(n1) + 3) // 4) // (256 * max(1, int(unroll))))
+    want = -(-CHAIN_STEP_WG_PER_CU * cus // max(1, int(chains)))
+    return int(max(1, min(want, iters, L.CHAIN_STEP_MAX_BLOCKS_PER_CHAIN)))
+
+
+def chain_step_unrolls(method, noise_mode, collect=L.COLLECT_NONE):
+    """The unroll depths bdl_chain_step offers for this combination."""
+    return tuple(u for u in (1, 2, 4)
+                 if L.lib().bdl_chain_step_unroll_ok(int(method), int(noise_mode), int(collect), u))
+
+
+def chain_step_args(state, method, *, scalars, noise_mode, collect=L.COLLECT_NONE, mom1=None,
+                    mom2=None, collect_a=1.0, collect_b=1.0, first_step=False, momentum=False,
+                    seed=0, chain=0, step=0, div_mode=None, noise=None, blocks_per_chain=0,
+                    unroll=0, nonfinite_per_chain=None):
+    """The bdl_chain_step_args of a launch over `state` (see chain_step)."""
+    a = L.ChainStepArgs()
+    a.theta = state.theta.data_ptr()
+    g = getattr(state, "grad", None)
+    a.grad = None if g is None else g.data_ptr()
+    gb = getattr(state, "chain_gbase", None)
+    a.grad_base = None if gb is None else gb.data_ptr()
+    nf = getattr(state, "nonfinite", None)
+    a.nonfinite = None if nf is None else nf.data_ptr()
+    if nonfinite_per_chain is None:
+        nonfinite_per_chain = nf is not None and nf.numel() == int(state.K) and int(state.K) > 1
+    a.nonfinite_per_chain = 1 if nonfinite_per_chain else 0
+    a.mom = None if state.mom is None else state.mom.data_ptr()
+    a.prior_mean = None if state.prior is None else state.prior.data_ptr()
+    nz = noise if noise is not None else getattr(state, "noise", None)
+    a.noise = None if nz is None else nz.data_ptr()
+    a.mom1 = None if mom1 is None else mom1.data_ptr()
+    a.mom2 = None if mom2 is None else mom2.data_ptr()
+    a.runs = state.chain_runs.data_ptr()
+    a.nruns = int(state.chain_nruns)
+    a.scalars = scalars.data_ptr()
+    a.n1, a.chain_groups, a.chains = int(state.n1), int(state.chain_groups), int(state.K)
+    a.method, a.noise_mode, a.collect = int(method), int(noise_mode), int(collect)
+    a.flags = ((L.FLAG_FIRST_STEP if first_step else 0) | (L.FLAG_MOMENTUM if momentum else 0)
+               | _div_flag(div_mode))
+    a.blocks_per_chain, a.unroll = int(blocks_per_chain), int(unroll)
+    a.collect_a, a.collect_b = float(collect_a), float(collect_b)
+    a.inv_collect_a, a.inv_collect_b = _inv(collect_a), _inv(collect_b)
+    a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    a.chain = int(chain) & 0xFFFFFFFFFFFFFFFF
+    a.step = int(step) & 0xFFFFFFFFFFFFFFFF
+    return a
+
+
+def chain_step(state, method, *, scalars, **kw):
+    """One fused step of K stacked chains, each with its own hyperparameters
+    (bdl_chain_step, include/bdl_chain_step.h).  `state`: the stacked vectors
+    (theta, grad or None, mom, prior, noise, nonfinite), K, n1, chain_groups and
+    ONE chain's run table in chain-local indices (chain_runs, chain_nruns;
+    chain_gbase: the [K, nruns] gradient-base table or None) — a StackedState
+    built with chain_tables=True.  `scalars`: a device [K, 12] float32 row
+    block (L.CHAIN_SCALAR_COLUMNS; per_chain.csghmc_rows / sgld_rows), 16-B
+    aligned; row k is chain k's lr, noise scale, 1 - alpha, prior_sig, sigma2,
+    n_data, mu and reciprocals.  method: L.CSGHMC or L.SGLD.  One launch on the
+    current stream, no host synchronisation, no copy.  blocks_per_chain 0: from
+    K, n1 and the CU count (chain_step_blocks_per_chain); values never depend
+    on it, nor on unroll."""
+    K_ = int(state.K)
+    if (scalars.dtype != torch.float32 or not scalars.is_cuda or not scalars.is_contiguous()
+            or scalars.numel() != K_ * 12 or scalars.device != state.theta.device):
+        raise ValueError("chain_step: scalars must be a contiguous float32 [K, 12] tensor on the "
+                         "state's device")
+    if not kw.get("blocks_per_chain"):
+        kw["blocks_per_chain"] = chain_step_blocks_per_chain(state.n1, K_, state.theta.device,
+                                                             kw.get("unroll") or 1)
+    a = chain_step_args(state, method, scalars=scalars, **kw)
+    dev = state.theta.device
+    t = getattr(state, "timer", None)
+    e0 = t.begin() if t is not None else None
+    L.check(L.lib().bdl_chain_step(a, L.current_stream_handle(dev)), "bdl_chain_step")
+    if e0 is not None:
+        t.end(e0, alg_bytes_per_elem(a) * int(a.n1) * K_)
+
+
 def philox_normal(n, seed, chain, step, device="cuda"):
     """The N(0,1) values the step kernel draws in Philox mode, as a tensor."""
     out = torch.empty(n, dtype=torch.float32, device=device)

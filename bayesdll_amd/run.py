@@ -112,7 +112,52 @@ def build_parser():
     ap.add_argument("--rhat", action="store_true",
                     help="with --stacked_chains >= 2: log the cross-chain R-hat of the collected "
                          "moments at every evaluation (stacked diagnostics())")
+    ap.add_argument("--sweep", action="append", default=[], metavar="NAME=v1,...,vK",
+                    help="with --stacked_chains K (csghmc, sgld, csgld): chain k runs with the "
+                         "k-th value of NAME (lr, lr_head, prior_sig, nd, Ninflate, and "
+                         "momentum_decay or momentum); one value is broadcast; repeatable. "
+                         "Every chain is scored on its own at each evaluation")
     return ap
+
+
+def parse_sweep(ap, args):
+    """--sweep NAME=v1,...,vK items -> {name: K floats} (ap.error on anything
+    the per-chain launch cannot run)."""
+    from .per_chain import NAMES
+    if not args.sweep:
+        return None
+    K = args.stacked_chains
+    if K <= 0:
+        ap.error("--sweep gives every stacked chain its own hyperparameters: it needs "
+                 "--stacked_chains K > 0")
+    fam = {"csghmc": "csghmc", "sgld": "sgld", "csgld": "sgld"}.get(args.method)
+    if fam is None:
+        ap.error(f"--sweep: {args.method} has no per-chain launch (csghmc, sgld or csgld)")
+    if args.clip_grad is not None:
+        ap.error("--sweep cannot be combined with --clip_grad (the clipped step has no per-chain "
+                 "launch)")
+    if args.rhat:
+        ap.error("--sweep cannot be combined with --rhat (R-hat compares chains that target one "
+                 "posterior)")
+    out = {}
+    for item in args.sweep:
+        name, eq, vals = item.partition("=")
+        if not eq or not vals:
+            ap.error(f"--sweep {item!r}: expected NAME=v1,...,vK")
+        if name not in NAMES[fam]:
+            ap.error(f"--sweep: {args.method} does not sweep {name!r} (" + ", ".join(NAMES[fam]) + ")")
+        if name in out:
+            ap.error(f"--sweep: {name!r} given twice")
+        try:
+            v = [float(x) for x in vals.split(",")]
+        except ValueError:
+            ap.error(f"--sweep {item!r}: values must be numbers")
+        if len(v) == 1:
+            v = v * K
+        if len(v) != K:
+            ap.error(f"--sweep {name}: {len(v)} values for --stacked_chains {K} (length mismatch)")
+        out[name] = v
+    return out
 
 
 class SyntheticLoader:
@@ -155,6 +200,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.rhat and args.stacked_chains < 2:
         ap.error("--rhat compares the chains of one device: it needs --stacked_chains >= 2")
+    sweep = parse_sweep(ap, args)
     from . import chains
     rank, world, device = chains.init_chains()
     if device.type != "cuda":
@@ -216,11 +262,23 @@ def main(argv=None):
             raise ValueError(f"--stacked_chains: {args.method} is not stacked (csghmc, sghmc, "
                              "sgld, csgld, adam_sghmc or adam_csghmc; csghmc_fs runs one chain "
                              "per process)")
+        kw = {} if sweep is None else {"per_chain": sweep}
         S = cls(net, args.stacked_chains, args, logger=logger, init="reinit", graph=args.graph,
-                net0=net0)
+                net0=net0, **kw)
         logger.info(f"{args.stacked_chains} stacked chains on this device "
                     f"(chain ids {S.chain0}..{S.chain0 + S.K - 1})")
-        return S.train(train_loader, test_loader)
+        hist = S.train(train_loader, test_loader)
+        if sweep is not None:
+            # rank the sweep on held-out data (the test split without one)
+            from .per_chain import describe
+            which, loader = ("validation", val_loader) if val_loader is not None \
+                else ("test", test_loader)
+            nll, err = S.evaluate_chains(loader)
+            best = int(np.argmin(np.where(np.isfinite(nll), nll, np.inf)))
+            logger.info(f"best chain by {which} NLL: chain {S.chain0 + best} "
+                        f"({describe(S.per_chain, S.swept, best)}): loss = {nll[best]:.4f}, "
+                        f"error = {err[best]:.4f}")
+        return hist
     runner_cls = importlib.import_module(f"bayesdll_amd.{args.method}").Runner
     runner = runner_cls(net, net0, args, logger)
     return runner.train(train_loader, val_loader, test_loader)

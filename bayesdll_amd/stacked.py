@@ -47,6 +47,7 @@ from torch.func import functional_call, grad_and_value, vmap
 
 from . import _lib as L
 from . import kernels as K
+from . import per_chain as PC
 from ._base import no_gc
 from ._runner import EVAL_STEP_BASE
 from .cyclical import CyclicalSGMCMC
@@ -62,8 +63,13 @@ class StackedState:
     chain_groups, nonfinite) are what kernels._step_args reads."""
 
     def __init__(self, net, K_, *, readout_name=None, bias="informative", init="copy",
-                 seed=0, need_mom=True, need_prior=False, net0=None):
+                 seed=0, need_mom=True, need_prior=False, net0=None, chain_tables=False):
         import torch.nn as nn
+        # chain_tables: describe the launch per chain (kernels.chain_step): ONE
+        # chain's run table in chain-local indices (chain_runs, chain_nruns)
+        # and a [K, nruns] gradient-base table (chain_gbase), one divergence
+        # flag per chain
+        self.chain_tables = bool(chain_tables)
         if K_ < 1:
             raise ValueError("StackedState: K must be >= 1")
         for m in net.modules():
@@ -136,7 +142,18 @@ class StackedState:
         self.grad_mode = "tensor" if self.K * (len(self.names) + gap) <= MAX_TENSOR_RUNS else "flat"
         self.grad, self.gbase, self._tables = None, None, {}
         self._gbound, self._seg_tables = None, {}  # grad_segments: what use_grads bound last
-        if self.grad_mode == "flat":
+        self.chain_runs, self.chain_nruns, self.chain_gbase = None, 0, None
+        if self.chain_tables:
+            # one run per tensor whatever K is: the in-place form serves any K
+            self.grad_mode = "tensor" if len(self.names) <= L.CHAIN_STEP_MAX_RUNS_BASES else "flat"
+            self.nonfinite = torch.zeros(self.K, dtype=torch.int32, device=dev)
+            self.runs, self.nruns = None, 0
+            if self.grad_mode == "flat":
+                self.grad2d = torch.zeros(self.K, self.stride, **f32)
+                self.grad = self.grad2d.view(-1)
+                self.chain_runs = build_runs(self.offsets, self.numels, self.attrs, self.n1).to(dev)
+                self.chain_nruns = int(self.chain_runs.shape[0])
+        elif self.grad_mode == "flat":
             self.grad2d = torch.zeros(self.K, self.stride, **f32)
             self.grad = self.grad2d.view(-1)
             offs, nums, ats = [], [], []
@@ -184,11 +201,37 @@ class StackedState:
         key = self._gbound = tuple(ptrs)
         tab = self._tables.get(key)
         if tab is None:
-            tab = self._build_table(ptrs)
+            tab = self._build_chain_table(ptrs) if self.chain_tables else self._build_table(ptrs)
             if len(self._tables) >= 8:
                 self._tables.pop(next(iter(self._tables)))
             self._tables[key] = tab
-        self.runs, self.nruns, self.gbase = tab
+        if self.chain_tables:
+            self.chain_runs, self.chain_nruns, self.chain_gbase = tab
+        else:
+            self.runs, self.nruns, self.gbase = tab
+
+    def _build_chain_table(self, ptrs):
+        """The per-chain form (include/bdl_chain_step.h): ONE chain's runs in
+        chain-local indices, one per tensor and no padding run (the launch
+        ends at n1), and a [K, nruns] base table whose row k holds
+        &g_t[k, 0] - 4 * offset_t; a tensor for which any chain's base is not
+        16-byte addressable is marked GUNALIGNED in the shared run table."""
+        rows, bases = [], np.zeros((self.K, len(ptrs)), dtype=np.int64)
+        for i, (o, n, a, ptr) in enumerate(zip(self.offsets, self.numels, self.attrs, ptrs)):
+            at = a | (0 if ptr else L.ATTR_SKIP)
+            if ptr:
+                b = ptr + 4 * n * np.arange(self.K, dtype=np.int64) - 4 * o
+                bases[:, i] = b
+                if (b % 16).any():
+                    at |= L.ATTR_GUNALIGNED
+            rows.append((o + n, at))
+        nt = len(rows)
+        host = torch.empty(2 * nt + self.K * nt, dtype=torch.int64).pin_memory()
+        h = host.numpy()
+        h[:2 * nt] = np.asarray(rows, dtype=np.int64).reshape(-1)
+        h[2 * nt:] = bases.reshape(-1)
+        dev = host.to(self.device, non_blocking=True)
+        return dev[:2 * nt].view(nt, 2), nt, dev[2 * nt:].view(self.K, nt)
 
     def _build_table(self, ptrs):
         """One run per (chain, tensor) — a run must not span two gradient
@@ -244,10 +287,18 @@ class StackedState:
         return tab
 
     def diverged(self, reset=True):
-        bad = bool(self.nonfinite.item())
+        bad = bool(self.nonfinite.any().item())
         if bad and reset:
             self.nonfinite.zero_()
         return bad
+
+    def diverged_chains(self, reset=True):
+        """The chains that wrote a non-finite theta (per-chain flags:
+        chain_tables); with one shared flag, all chains or none."""
+        nf = self.nonfinite.cpu().numpy() != 0
+        if nf.any() and reset:
+            self.nonfinite.zero_()
+        return [k for k in range(self.K) if nf[k if nf.size == self.K else 0]]
 
 
 def st_big(st):
@@ -269,10 +320,33 @@ class _StackedSampler:
     last_clip = None
     _clip_ws = None
 
+    # the family of per-chain hyperparameters this sampler sweeps
+    # (per_chain.NAMES), None where no per-chain launch exists
+    per_chain_family = None
+    per_chain = None   # {name: float64 [K]} over the family's names, or None (uniform)
+    swept = ()         # the names the caller gave
+
+    def _init_per_chain(self, per_chain, K_, args):
+        """Validate `per_chain` before anything touches the device."""
+        if per_chain is None or len(per_chain) == 0:
+            return
+        fam = self.per_chain_family
+        if fam is None:
+            raise ValueError(f"{type(self).__name__}: per_chain is not supported (the per-chain "
+                             "launch covers cSGHMC and SGLD / cSGLD; SGHMC and the Adam samplers "
+                             "share one set of hyperparameters)")
+        if isinstance(self, StackedCSGLD) and getattr(args, "clip_grad", None) is not None:
+            raise ValueError(f"{type(self).__name__}: per_chain cannot be combined with clip_grad "
+                             "(the clipped step has no per-chain launch)")
+        self.per_chain = PC.parse(per_chain, K_, fam, PC.defaults(args, fam))
+        self.swept = tuple(nm for nm in PC.NAMES[fam] if nm in per_chain)
+
     def __init__(self, net, K_, args, *, chain0=None, seed=None, init="copy", criterion=None,
-                 per_chain_batches=False, logger=None, graph=None, net0=None):
+                 per_chain_batches=False, logger=None, graph=None, net0=None, per_chain=None):
         from . import chains
         from ._base import default_graph
+        self._init_per_chain(per_chain, K_, args)
+        self._rows_dev = None  # (epoch key, [batches, K, 12] device rows) of a per_chain epoch
         self.args, self.logger = args, logger
         # replay the vmapped forward/backward from a captured HIP graph (per
         # input shape): the vmap dispatch costs ~1.2 ms of host time per step
@@ -288,10 +362,11 @@ class _StackedSampler:
         # re-initialisation seeds seed + chain id: distinct across processes too
         self.state = StackedState(self.net, K_, bias=str(hp["bias"]), init=init,
                                   seed=self.seed + self.chain0, need_prior=self.need_prior,
-                                  net0=net0)
+                                  net0=net0, chain_tables=self.per_chain is not None)
         self.K = K_
-        # launch geometry tuned for the stacked size (speed only)
-        if st_big(self.state):
+        # launch geometry tuned for the stacked size (speed only; the per-chain
+        # launch has its own, kernels.chain_step_blocks_per_chain)
+        if st_big(self.state) and self.per_chain is None:
             # (scratch on plain allocations, as the stacked state's own vectors)
             self.state.launch_cfg = K.autotune_once(self.state.n, self.state.device,
                                                     self.tune_method)
@@ -395,6 +470,13 @@ class _StackedSampler:
         self.last_clip = K.chain_clip(seg, nseg, self.K, self.clip_grad, workspace=self._clip_ws,
                                       blocks_per_chain=self._clip_bpc)
 
+    def _upload_rows(self, rows):
+        """Host fp32 rows ([K, 12] or [batches, K, 12]) to the device in one
+        asynchronous copy from pinned memory; a row block is 48 * K bytes, so
+        every block of the device array is 16-byte aligned."""
+        host = torch.from_numpy(np.array(rows, dtype=np.float32, order="C")).pin_memory()
+        return host.to(self.state.device, non_blocking=True)
+
     def _accumulate(self, acc, loss, out, y):
         """Per-chain running (loss sum, error count, examples) on the device."""
         bs = y.shape[-1]
@@ -424,12 +506,17 @@ class _StackedSampler:
         draws or means); the chains' current theta while none is collected.
         With one process per GPU (torch.distributed initialised) the
         processes' stacked predictives are averaged too
-        (chains.average_predictive: one all-reduce)."""
+        (chains.average_predictive: one all-reduce).  With per_chain the chains
+        are different models, so this uniform mixture mixes different models
+        (an ensemble over the sweep); `evaluate_chains` scores each alone."""
         from . import chains
         lp = self._local_logprob(x)
         return chains.average_predictive(lp) if chains.world() > 1 else lp
 
-    def _local_logprob(self, x):
+    def _component_logprobs(self, x):
+        """[K, B, C] log-probabilities of every chain under each collected
+        component (`_components`: its draws, its keys), or under the chains'
+        current theta while nothing is collected."""
         st = self.state
         with torch.no_grad():
             buf = torch.empty_like(st.theta)
@@ -438,8 +525,43 @@ class _StackedSampler:
             comps = [F.log_softmax(self._fwd(views, x), dim=-1) for _ in self._components(buf)]
             if not comps:
                 comps = [F.log_softmax(self.chain_logits(x), dim=-1)]
-            lp = torch.cat(comps, 0)  # [K * components, B, C]
+            return comps
+
+    def _local_logprob(self, x):
+        with torch.no_grad():
+            lp = torch.cat(self._component_logprobs(x), 0)  # [K * components, B, C]
             return lp.logsumexp(0) - math.log(lp.shape[0])
+
+    def chain_logprob(self, x):
+        """[K, B, C]: every chain's OWN predictive, log of its probability
+        averaged uniformly over that chain's components."""
+        with torch.no_grad():
+            lp = torch.stack(self._component_logprobs(x), 0).double()  # [components, K, B, C]
+            return lp.logsumexp(0) - math.log(lp.shape[0])
+
+    def evaluate_chains(self, loader):
+        """(nll [K], err [K]) over a data loader, chain by chain: each chain is
+        scored from its own collected components (the draws and keys
+        `_components` uses) or from its current theta while nothing is
+        collected.  What ranks a per_chain sweep; applies to any stacked
+        sampler.  One host read at the end."""
+        dev = self.args.device
+        nll = torch.zeros(self.K, dtype=torch.float64, device=dev)
+        err = torch.zeros(self.K, dtype=torch.int64, device=dev)
+        nb = 0
+        was = self.net.training
+        self.net.eval()
+        try:
+            for x, y in loader:
+                x, y = x.to(dev), y.to(dev)
+                lp = self.chain_logprob(x)
+                nll -= lp.gather(-1, y.view(1, -1, 1).expand(self.K, -1, 1)).squeeze(-1) \
+                    .double().sum(-1)
+                err += lp.argmax(-1).ne(y).sum(-1)
+                nb += len(y)
+        finally:
+            self.net.train(was)
+        return (nll / nb).cpu().numpy(), (err.double() / nb).cpu().numpy()
 
     def _sample(self, out, mean, m2, var_mode, ratio):
         """One posterior draw of every chain into `out` ([K*stride]); chain k
@@ -479,6 +601,10 @@ class _StackedSampler:
         sampler owns is written."""
         if self.K < 2:
             raise ValueError("diagnostics: R-hat compares chains; this sampler runs K = 1")
+        if self.per_chain is not None:
+            raise ValueError("diagnostics: this sampler runs per_chain hyperparameters; R-hat "
+                             "compares chains that target ONE posterior, and these chains "
+                             "target different ones (rank them with evaluate_chains)")
         if component is None:
             component = self._latest_component()
         m1 = None
@@ -530,7 +656,8 @@ class _StackedSampler:
         d = {"stacked": type(self).__name__, "K": self.K, "chain0": self.chain0,
              "seed": self.seed, "n": st.n1, "stride": st.stride, "theta": st.theta,
              "mom": st.mom, "prior": st.prior, "step_count": self.step_count,
-             "draws": self.draws}
+             "draws": self.draws,
+             "per_chain": None if self.per_chain is None else PC.table_for_state(self.per_chain)}
         d.update(self._extra_state())
         return d
 
@@ -545,6 +672,10 @@ class _StackedSampler:
         if (d.get("stacked") != type(self).__name__ or d["K"] != self.K or d["n"] != st.n1
                 or d["stride"] != st.stride):
             raise ValueError("load_ckpt: checkpoint of a different stacked sampler / network")
+        mine = None if self.per_chain is None else PC.table_for_state(self.per_chain)
+        if d.get("per_chain") != mine:
+            raise ValueError("load_ckpt: the checkpoint's per_chain table differs from this "
+                             "sampler's (the chains would continue under other hyperparameters)")
         with torch.no_grad():
             st.theta.copy_(d["theta"])
             for mine, theirs in ((st.mom, d["mom"]), (st.prior, d["prior"])):
@@ -582,10 +713,24 @@ class _StackedSampler:
                 rec["test"] = self.evaluate(test_loader)
                 log(f"(Epoch {ep}) stacked predictive: loss = {rec['test'][0]:.4f}, "
                     f"error = {rec['test'][1]:.4f}")
+                if self.per_chain is not None:
+                    self._report_chains(ep, rec, test_loader, log)
                 if getattr(self.args, "rhat", False):  # opt-in (run.py --rhat)
                     self._report_rhat(ep, rec, log)
             hist.append(rec)
         return hist
+
+    def _report_chains(self, ep, rec, loader, log):
+        """One log line per chain of a per_chain sweep — its swept values, NLL
+        and error (`evaluate_chains`) — and rec["chains"]; the best chain so
+        far by NLL in rec["best"]."""
+        nll, err = self.evaluate_chains(loader)
+        rec["chains"] = {"nll": nll.tolist(), "error": err.tolist()}
+        for k in range(self.K):
+            log(f"(Epoch {ep}) chain {self.chain0 + k}: {PC.describe(self.per_chain, self.swept, k)}"
+                f": loss = {nll[k]:.4f}, error = {err[k]:.4f}")
+        ok = np.where(np.isfinite(nll), nll, np.inf)
+        rec["best"] = int(np.argmin(ok))
 
     def _report_rhat(self, ep, rec, log):
         """One log line and rec["rhat"] from `diagnostics()`; an evaluation
@@ -621,13 +766,43 @@ class StackedCSGHMC(_StackedSampler):
                                     proportion_exploration=getattr(args, "proportion_exploration",
                                                                    0.5))
         self.samples_per_cycle, self.mom1, self.mom2 = {}, {}, {}
+        if self.per_chain is not None:
+            # chain k's own schedule: its lr is a one-chain sampler's with lr_k
+            self.scheds = PC.schedules(self.per_chain, args.epochs, self.sched.number_of_cycles,
+                                       self.sched.proportion_exploration)
 
-    def update(self, grads, lr, should_sample=False, collect=None):
+    per_chain_family = "csghmc"
+
+    def chain_rows(self, lr):
+        """[..., K, 12] fp32 scalar rows for body lrs `lr` ([..., K] float64)."""
+        return PC.csghmc_rows(self.per_chain, lr, self.args.ND)
+
+    def epoch_rows(self, epoch, bpe):
+        """The [bpe, K, 12] rows of one epoch: every chain's cyclical lr at
+        every batch, expanded on the host."""
+        lrs = np.stack([PC.cyclical_lrs(self.scheds, epoch, b, bpe) for b in range(bpe)])
+        return self.chain_rows(lrs)
+
+    def update(self, grads, lr, should_sample=False, collect=None, rows=None):
         """The fused launch over all chains for given gradients (step's second
         half): v <- v(1-a) - lr(g + prior_sig theta) [+ noise]; theta += v;
-        Welford collect on sample steps."""
+        Welford collect on sample steps.  With per_chain, `lr` is the body lr
+        per chain ([K]; a scalar is every chain's) and the launch reads chain
+        k's scalars from `rows` (a device [K, 12] block; None: formed from lr
+        and uploaded here)."""
         args, st = self.args, self.state
         st.use_grads(grads)
+        if self.per_chain is not None:
+            if rows is None:
+                lr_k = np.broadcast_to(np.asarray(lr, dtype=np.float64), (self.K,))
+                rows = self._upload_rows(self.chain_rows(lr_k))
+            ckind, m1, m2, ca = (L.COLLECT_NONE, None, None, 1.0) if collect is None else collect
+            K.chain_step(st, L.CSGHMC, scalars=rows,
+                         noise_mode=L.NOISE_PHILOX if should_sample else L.NOISE_NONE,
+                         collect=ckind, mom1=m1, mom2=m2, collect_a=ca, seed=self.seed,
+                         chain=self.chain0, step=self.step_count)
+            self.step_count += 1
+            return
         lrs = (lr, lr * (args.lr_head / args.lr))
         N = args.ND * self.Ninflate
         ns = [self.nd * np.sqrt(2 * self.momentum_decay * v) / N for v in lrs]
@@ -659,6 +834,8 @@ class StackedCSGHMC(_StackedSampler):
         sched.current_epoch = epoch
         bpe = len(loader)
         acc = self._new_acc()
+        # per_chain: the epoch's rows in one upload, row b handed to step b
+        rows = None if self.per_chain is None else self._upload_rows(self.epoch_rows(epoch, bpe))
         for b, (x, y) in enumerate(loader):
             x, y = x.to(dev, non_blocking=True), y.to(dev, non_blocking=True)
             lr = sched.calculate_lr(epoch=epoch, batch=b, batches_per_epoch=bpe)
@@ -668,7 +845,8 @@ class StackedCSGHMC(_StackedSampler):
             if ss:
                 c = sched.get_cycle_number(epoch=epoch, batch=b, batches_per_epoch=bpe)
                 collect, cnt = self._collect_spec(c)
-            loss, out = self.step(x, y, lr, should_sample=ss, collect=collect)
+            kw = {} if rows is None else {"rows": rows[b]}
+            loss, out = self.step(x, y, lr, should_sample=ss, collect=collect, **kw)
             if ss:  # Q2: the reference bumps the count twice per sample
                 self.samples_per_cycle[c] = cnt + 1
             self._accumulate(acc, loss, out, y)
@@ -742,26 +920,53 @@ class StackedSGLD(_StackedSampler):
 
     need_prior = True
     tune_method = "sgld"
+    per_chain_family = "sgld"
 
     def __init__(self, net, K_, args, **kw):
         super().__init__(net, K_, args, **kw)
         self.burnin = int(args.hparams["burnin"])
         self.mu = float(getattr(args, "momentum", 0.0))
+        if self.per_chain is not None:  # all zero or all non-zero (per_chain.parse)
+            self.mu = float(self.per_chain["momentum"][0])
         self.has_buffer = False
         self.bi = 0                      # global iteration count thinning uses
         self.m1 = self.m2 = None
         self.cnt = 0
 
-    def update(self, grads, lrs, collect=None):
+    def chain_rows(self, lr, lr_head):
+        """[..., K, 12] fp32 scalar rows for body / head lrs ([..., K] float64)."""
+        return PC.sgld_rows(self.per_chain, lr, lr_head, self.args.ND)
+
+    def epoch_rows(self, epoch, bpe):
+        """The [bpe, K, 12] rows of one epoch (constant lr: the same row block
+        at every batch)."""
+        r = self.chain_rows(self.per_chain["lr"], self.per_chain["lr_head"])
+        return np.broadcast_to(r, (bpe,) + r.shape)
+
+    def update(self, grads, lrs, collect=None, rows=None):
         """The fused SGLD + SGD(momentum mu) launch over all chains
-        (methods/sgld.py:469-484 + :226), optional running-moment collect."""
+        (methods/sgld.py:469-484 + :226), optional running-moment collect.
+        With per_chain, lrs = (body, head) lr per chain ([K] each; a scalar is
+        every chain's) and the launch reads chain k's scalars from `rows` (a
+        device [K, 12] block; None: formed from lrs and uploaded here)."""
         args, st = self.args, self.state
         st.use_grads(grads)
-        N = args.ND * self.Ninflate
-        ns = [self.nd * np.sqrt(2 / (N * v)) for v in lrs]
         mom = self.mu != 0
         ckind, m1, m2, ca, cb = (L.COLLECT_NONE, None, None, 1.0, 1.0) if collect is None \
             else collect
+        if self.per_chain is not None:
+            if rows is None:
+                l0, l1 = (np.broadcast_to(np.asarray(v, dtype=np.float64), (self.K,)) for v in lrs)
+                rows = self._upload_rows(self.chain_rows(l0, l1))
+            K.chain_step(st, L.SGLD, scalars=rows, noise_mode=L.NOISE_PHILOX,
+                         first_step=mom and not self.has_buffer, momentum=mom, collect=ckind,
+                         mom1=m1, mom2=m2, collect_a=ca, collect_b=cb, seed=self.seed,
+                         chain=self.chain0, step=self.step_count)
+            self.has_buffer = self.has_buffer or mom
+            self.step_count += 1
+            return
+        N = args.ND * self.Ninflate
+        ns = [self.nd * np.sqrt(2 / (N * v)) for v in lrs]
         key = dict(seed=self.seed, chain=self.chain0, step=self.step_count)
         sgd_kw = dict(mu=self.mu, first_step=mom and not self.has_buffer, momentum=mom,
                       collect=ckind, mom1=m1, mom2=m2, collect_a=ca, collect_b=cb)
@@ -798,13 +1003,16 @@ class StackedSGLD(_StackedSampler):
         collect = epoch >= self.burnin
         lrs = (args.lr, args.lr_head)
         acc = self._new_acc()
+        # per_chain: the epoch's rows in one upload (one block: the lr is constant)
+        kw = {} if self.per_chain is None else \
+            {"rows": self._upload_rows(self.epoch_rows(epoch, 1))[0]}
         for x, y in loader:
             x, y = x.to(dev, non_blocking=True), y.to(dev, non_blocking=True)
             spec = None
             do_collect = collect and (self.bi + 1) % self.thin == 0
             if do_collect:  # methods/sgld.py:239-246
                 spec = (L.COLLECT_MEAN, self.m1, self.m2, float(self.cnt), float(self.cnt + 1))
-            loss, out = self.step(x, y, lrs, collect=spec)
+            loss, out = self.step(x, y, lrs, collect=spec, **kw)
             if do_collect:
                 self.cnt += 1
             self.bi += 1
@@ -868,6 +1076,16 @@ class StackedCSGLD(StackedSGLD):
                                     proportion_exploration=getattr(args, "proportion_exploration",
                                                                    0.5))
         self.samples_per_cycle, self.mom1, self.mom2 = {}, {}, {}
+        if self.per_chain is not None:
+            # chain k's own schedule: its lr is a one-chain sampler's with lr_k
+            self.scheds = PC.schedules(self.per_chain, args.epochs, self.sched.number_of_cycles,
+                                       self.sched.proportion_exploration)
+
+    def epoch_rows(self, epoch, bpe):
+        """The [bpe, K, 12] rows of one epoch: every chain's cyclical lr (and
+        head lr = lr * (lr_head / lr_base)) at every batch."""
+        lrs = np.stack([PC.cyclical_lrs(self.scheds, epoch, b, bpe) for b in range(bpe)])
+        return self.chain_rows(lrs, PC.head_lrs(self.per_chain, lrs))
 
     def train_one_epoch(self, loader, epoch):
         args, dev, sched = self.args, self.args.device, self.sched
@@ -876,6 +1094,7 @@ class StackedCSGLD(StackedSGLD):
         bpe = len(loader)
         acc = self._new_acc()
         st = self.state
+        rows = None if self.per_chain is None else self._upload_rows(self.epoch_rows(epoch, bpe))
         for b, (x, y) in enumerate(loader):
             x, y = x.to(dev, non_blocking=True), y.to(dev, non_blocking=True)
             lr = sched.calculate_lr(epoch=epoch, batch=b, batches_per_epoch=bpe)
@@ -891,7 +1110,8 @@ class StackedCSGLD(StackedSGLD):
                 else:
                     cc = self.samples_per_cycle.get(c, 0) + 1
                     spec = (L.COLLECT_MEAN, self.mom1[c], self.mom2[c], float(cc - 1), float(cc))
-            loss, out = self.step(x, y, (lr, lr * (args.lr_head / args.lr)), collect=spec)
+            kw = {} if rows is None else {"rows": rows[b]}
+            loss, out = self.step(x, y, (lr, lr * (args.lr_head / args.lr)), collect=spec, **kw)
             if ss:
                 self.samples_per_cycle[c] = self.samples_per_cycle.get(c, 0) + 1
             if sched.last_in_cycle(epoch=epoch, batch=b, batches_per_epoch=bpe):
@@ -949,6 +1169,8 @@ class StackedSGHMC(StackedSGLD):
     launch for all chains — and the SGLD Runner's burn-in / thinned running
     moments.  `args` as the sghmc Runner's (hparams with momentum_decay)."""
 
+    per_chain_family = None  # no per-chain SGHMC launch
+
     def __init__(self, net, K_, args, **kw):
         super().__init__(net, K_, args, **kw)
         self.momentum_decay = float(args.hparams["momentum_decay"])
@@ -979,6 +1201,7 @@ class _AdamStep:
     stay as they are."""
 
     tune_method = "adam"
+    per_chain_family = None  # no per-chain Adam launch
     grad_is_mom = False  # the cyclical variant's p.grad = v_mom (adam_csghmc.py:834)
 
     def _init_adam(self):
