@@ -198,6 +198,32 @@ CHAIN_STEP_EXPORTS = {
     "bdl_chain_step": (C.c_int, [C.POINTER(ChainStepArgs), C.c_void_p]),
 }
 
+class StatsSegment(C.Structure):
+    """include/bdl_stats.h bdl_stats_segment (a row of the device table: five int64)."""
+    _fields_ = [("grad", _fp), ("numel", C.c_int64), ("grad_stride", C.c_int64),
+                ("offset", C.c_int64), ("lr_group", C.c_int64)]
+
+
+class StatsArgs(C.Structure):
+    """include/bdl_stats.h bdl_chain_stats_args."""
+    _fields_ = [("theta", _fp), ("mom", _fp), ("prior_mean", _fp), ("segments", _fp),
+                ("lr_table", _fp), ("acc", _fp), ("workspace", _fp),
+                ("chain_groups", C.c_uint64), ("nsegments", C.c_int32), ("chains", C.c_int32),
+                ("lr_row_stride", C.c_int32), ("accumulate", C.c_int32),
+                ("blocks_per_chain", C.c_int32), ("pad0", C.c_int32), ("lr", C.c_float * 2)]
+
+
+STATS_MAX_SEGMENTS, STATS_MAX_CHAINS, STATS_MAX_BLOCKS_PER_CHAIN = 65536, 65535, 256
+STATS_MAX_CHAIN_GROUPS = 1 << 40
+# the doubles of one (chain, segment) entry of acc, in order
+STATS_SUMS = ("G2", "V2", "D2", "DG", "VG", "V2L")
+
+# include/bdl_stats.h: additive to the ABI, as DIAG_EXPORTS
+STATS_EXPORTS = {
+    "bdl_chain_stats_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "bdl_chain_stats": (C.c_int, [C.POINTER(StatsArgs), C.c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -217,7 +243,8 @@ def lib():
             h = C.CDLL(LIB_PATH)
             for name, (res, argt) in (list(EXPORTS.items()) + list(DIAG_EXPORTS.items())
                                       + list(CLIP_EXPORTS.items())
-                                      + list(CHAIN_STEP_EXPORTS.items())):
+                                      + list(CHAIN_STEP_EXPORTS.items())
+                                      + list(STATS_EXPORTS.items())):
                 fn = getattr(h, name)
                 fn.restype = res
                 fn.argtypes = argt

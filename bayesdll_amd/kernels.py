@@ -545,6 +545,104 @@ def chain_clip(segments, nsegments, chains, max_norm, workspace=None, blocks_per
     return workspace[:2 * chains].view(chains, 2)
 
 
+def stats_bytes_per_elem(mom=True, prior=False):
+    """Algorithmic HBM bytes per element of one chain_stats call:
+    the gradient and theta, the momentum and the prior mean where bound, each
+    read once; nothing per element is written."""
+    return 8 + (4 if mom else 0) + (4 if prior else 0)
+
+
+def chain_stats_workspace(chains, nsegments, device):
+    """A fresh workspace for chain_stats over `chains` chains and `nsegments`
+    segments (a float64 tensor: the per-workgroup partial sums)."""
+    nbytes = int(L.lib().bdl_chain_stats_workspace_bytes(int(chains), int(nsegments)))
+    if nbytes <= 0:
+        raise ValueError(f"chain_stats: chains must be in [1, {L.STATS_MAX_CHAINS}] and nsegments "
+                         f"in [1, {L.STATS_MAX_SEGMENTS}] (got {chains}, {nsegments})")
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def stats_blocks_per_chain(numel, chains, device=None):
+    """Workgroups per chain for chain_stats over `numel` elements per chain:
+    one per 4096 elements (a full block iteration of the sweep), at most about
+    four per CU over all chains (clip_blocks_per_chain's rule, this sweep's cap)."""
+    cus = torch.cuda.get_device_properties(_device(device)).multi_processor_count
+    cap = max(1, -(-4 * cus // max(1, int(chains))))
+    return int(max(1, min(-(-int(numel) // 4096), cap, L.STATS_MAX_BLOCKS_PER_CHAIN)))
+
+
+def chain_stats(segments, nsegments, chains, chain_groups, theta, acc, *, mom=None,
+                prior_mean=None, lr=None, lr_table=None, lr_row_stride=12, accumulate=False,
+                workspace=None, blocks_per_chain=0):
+    """The per-(chain, tensor) sums G2, V2, D2, DG, VG and V2L = V2 / lr of K
+    stacked chains in one fused sweep (bdl_chain_stats, include/bdl_stats.h),
+    written into (accumulate False) or added to (True) `acc`, a device float64
+    [chains, nsegments, 6] tensor.  segments: the device table
+    (StackedState.stat_segments: an int64 [nsegments, 5] tensor of (gradient
+    base, numel, gradient chain stride, chain-local offset, lr group) rows);
+    theta / mom / prior_mean: the stacked [K * 4 * chain_groups] vectors.  The
+    lr comes from exactly one source: `lr` = (body, head) host floats for all
+    chains, or `lr_table`, a device float32 tensor whose row k (lr_row_stride
+    floats apart: 12 for a [K, 12] bdl_chain_scalars block) starts with chain
+    k's body / head lr.  Two launches on the current stream, no host
+    synchronisation.  Values do not depend on blocks_per_chain (0: the
+    library's default) beyond the fp64 summation order."""
+    if segments.dtype != torch.int64 or not segments.is_cuda or not segments.is_contiguous() \
+            or segments.numel() < 5 * int(nsegments):
+        raise ValueError("chain_stats: segments must be a contiguous int64 device tensor of "
+                         "nsegments x 5")
+    chains, nsegments, dev = int(chains), int(nsegments), segments.device
+    slot = 4 * int(chain_groups)
+    for nm, v in (("theta", theta), ("mom", mom), ("prior_mean", prior_mean)):
+        if v is None and nm != "theta":
+            continue
+        L.require_hip(v, nm)
+        if v.device != dev or not v.is_contiguous() or v.numel() < chains * slot:
+            raise ValueError(f"chain_stats: {nm} must be a contiguous stacked vector of "
+                             "chains * 4 * chain_groups elements on the segments' device")
+    if acc.dtype != torch.float64 or acc.device != dev or not acc.is_contiguous() \
+            or acc.numel() < chains * nsegments * len(L.STATS_SUMS):
+        raise ValueError("chain_stats: acc must be a contiguous float64 device tensor of "
+                         "chains x nsegments x 6")
+    if (lr is None) == (lr_table is None):
+        raise ValueError("chain_stats: give exactly one lr source (lr or lr_table)")
+    a = L.StatsArgs()
+    if lr is not None:
+        l0, l1 = (float(v) for v in lr)
+        if not (l0 > 0 and l1 > 0):
+            raise ValueError(f"chain_stats: lr must be > 0 for both groups (got {lr})")
+        a.lr[0], a.lr[1] = l0, l1
+    else:
+        L.require_hip(lr_table, "lr_table")
+        if lr_table.device != dev or int(lr_row_stride) < 2 or \
+                lr_table.numel() < (chains - 1) * int(lr_row_stride) + 2:
+            raise ValueError("chain_stats: lr_table must hold chains rows of lr_row_stride >= 2 "
+                             "floats on the segments' device")
+        a.lr_table, a.lr_row_stride = lr_table.data_ptr(), int(lr_row_stride)
+    if workspace is None:
+        workspace = _STATS_WS.get((dev.index, chains, nsegments))
+        if workspace is None:
+            workspace = _STATS_WS[(dev.index, chains, nsegments)] = \
+                chain_stats_workspace(chains, nsegments, dev)
+    elif workspace.dtype != torch.float64 or workspace.device != dev \
+            or not workspace.is_contiguous() or 8 * workspace.numel() < int(
+                L.lib().bdl_chain_stats_workspace_bytes(chains, nsegments)):
+        raise ValueError("chain_stats: workspace must be a contiguous float64 tensor of "
+                         "bdl_chain_stats_workspace_bytes(chains, nsegments) bytes on the "
+                         "segments' device")
+    a.theta = theta.data_ptr()
+    a.mom = None if mom is None else mom.data_ptr()
+    a.prior_mean = None if prior_mean is None else prior_mean.data_ptr()
+    a.segments, a.acc, a.workspace = segments.data_ptr(), acc.data_ptr(), workspace.data_ptr()
+    a.chain_groups, a.nsegments, a.chains = int(chain_groups), nsegments, chains
+    a.accumulate, a.blocks_per_chain = 1 if accumulate else 0, int(blocks_per_chain)
+    L.check(L.lib().bdl_chain_stats(a, L.current_stream_handle(dev)), "bdl_chain_stats")
+    return acc
+
+
+_STATS_WS = {}  # (device index, chains, nsegments) -> workspace (per-workgroup partials)
+
+
 CHAIN_STEP_WG_PER_CU = 2  # default grid of chain_step: about this many workgroups per CU
 
 

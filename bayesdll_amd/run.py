@@ -117,7 +117,23 @@ def build_parser():
                          "k-th value of NAME (lr, lr_head, prior_sig, nd, Ninflate, and "
                          "momentum_decay or momentum); one value is broadcast; repeatable. "
                          "Every chain is scored on its own at each evaluation")
+    ap.add_argument("--health", type=int, default=0, metavar="M",
+                    help="with --stacked_chains >= 1: every M-th step, accumulate the per-chain, "
+                         "per-tensor statistics between backward and update (one fused sweep) "
+                         "and log every chain's health after each epoch: kinetic and "
+                         "configurational temperature and the hottest tensor (csghmc), the "
+                         "largest gradient rms otherwise; works with --sweep")
     return ap
+
+
+def check_health(ap, args):
+    """--health M needs stacked chains and M >= 0 (ap.error otherwise)."""
+    if args.health < 0:
+        ap.error("--health: M must be >= 0")
+    if args.health and args.stacked_chains < 1:
+        ap.error("--health reads the stacked chains' statistics sweep: it needs "
+                 "--stacked_chains >= 1")
+    return args.health
 
 
 def parse_sweep(ap, args):
@@ -201,6 +217,7 @@ def main(argv=None):
     if args.rhat and args.stacked_chains < 2:
         ap.error("--rhat compares the chains of one device: it needs --stacked_chains >= 2")
     sweep = parse_sweep(ap, args)
+    check_health(ap, args)
     from . import chains
     rank, world, device = chains.init_chains()
     if device.type != "cuda":
@@ -263,6 +280,8 @@ def main(argv=None):
                              "sgld, csgld, adam_sghmc or adam_csghmc; csghmc_fs runs one chain "
                              "per process)")
         kw = {} if sweep is None else {"per_chain": sweep}
+        if args.health:
+            kw["health_every"] = args.health
         S = cls(net, args.stacked_chains, args, logger=logger, init="reinit", graph=args.graph,
                 net0=net0, **kw)
         logger.info(f"{args.stacked_chains} stacked chains on this device "

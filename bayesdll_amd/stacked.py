@@ -142,6 +142,7 @@ class StackedState:
         self.grad_mode = "tensor" if self.K * (len(self.names) + gap) <= MAX_TENSOR_RUNS else "flat"
         self.grad, self.gbase, self._tables = None, None, {}
         self._gbound, self._seg_tables = None, {}  # grad_segments: what use_grads bound last
+        self._stat_tables = {}                     # stat_segments, per bound gradient set
         self.chain_runs, self.chain_nruns, self.chain_gbase = None, 0, None
         if self.chain_tables:
             # one run per tensor whatever K is: the in-place form serves any K
@@ -286,6 +287,34 @@ class StackedState:
             self._seg_tables[key] = tab
         return tab
 
+    def stat_segments(self):
+        """(device table, nsegments, tensor indices) of kernels.chain_stats for
+        the gradients `use_grads` last bound: one (gradient base, numel,
+        gradient chain stride, chain-local offset, lr group) row per tensor
+        that has a gradient (include/bdl_stats.h); the gradient addressed as in
+        `grad_segments`, the lr group 1 for the readout (ATTR_HEAD), else 0.  A
+        frozen tensor / a missing gradient gets no row, a chain's padding lies
+        in none.  Cached per set of gradient addresses, as the run tables."""
+        key = self._gbound
+        if key is None:
+            raise ValueError("StackedState: stat_segments before use_grads")
+        tab = self._stat_tables.get(key)
+        if tab is None:
+            flat = self.grad_mode == "flat"
+            idx = [i for i, have in enumerate(key) if have]
+            if not idx:
+                raise ValueError("StackedState: no tensor has a gradient to take statistics of")
+            rows = [(self.grad.data_ptr() + 4 * self.offsets[i] if flat else key[i],
+                     self.numels[i], self.stride if flat else self.numels[i], self.offsets[i],
+                     1 if self.attrs[i] & L.ATTR_HEAD else 0) for i in idx]
+            host = torch.empty(len(rows), 5, dtype=torch.int64).pin_memory()
+            host.numpy()[:] = np.asarray(rows, dtype=np.int64)
+            tab = (host.to(self.device, non_blocking=True), len(rows), tuple(idx))
+            if len(self._stat_tables) >= 8:
+                self._stat_tables.pop(next(iter(self._stat_tables)))
+            self._stat_tables[key] = tab
+        return tab
+
     def diverged(self, reset=True):
         bad = bool(self.nonfinite.any().item())
         if bad and reset:
@@ -342,10 +371,17 @@ class _StackedSampler:
         self.swept = tuple(nm for nm in PC.NAMES[fam] if nm in per_chain)
 
     def __init__(self, net, K_, args, *, chain0=None, seed=None, init="copy", criterion=None,
-                 per_chain_batches=False, logger=None, graph=None, net0=None, per_chain=None):
+                 per_chain_batches=False, logger=None, graph=None, net0=None, per_chain=None,
+                 health_every=0):
         from . import chains
         from ._base import default_graph
         self._init_per_chain(per_chain, K_, args)
+        if int(health_every) != health_every or int(health_every) < 0:
+            raise ValueError(f"health_every must be an integer >= 0 (got {health_every!r})")
+        # every m-th step the statistics sweep runs between gradients() and
+        # update() (0: never; then step() is unchanged and nothing is allocated)
+        self.health_every = int(health_every)
+        self._health = None  # [acc [K, T, 6] float64, workspace, steps, tensor indices, bpc]
         self._rows_dev = None  # (epoch key, [batches, K, 12] device rows) of a per_chain epoch
         self.args, self.logger = args, logger
         # replay the vmapped forward/backward from a captured HIP graph (per
@@ -453,8 +489,132 @@ class _StackedSampler:
         launch (`update`).  Returns per-chain (loss [K], logits [K, B, C]) on
         the device, without a host sync."""
         grads, loss, out = self.gradients(x, y)
+        if self.health_every and self.step_count % self.health_every == 0:
+            kw = self._health_sweep(grads, a, kw)
         self.update(grads, *a, **kw)
         return loss, out
+
+    # --------------------------------------------------------------- health
+    def _health_lr(self, lrs, collect=None, rows=None):
+        """The sweep's lr source for a step with `update`'s arguments: ((body,
+        head) host floats, None, False) for uniform chains, (None, the [K, 12]
+        device rows of this step, whether they were formed and uploaded here
+        because the caller passed none) under per_chain.  The SGLD family's
+        form; cSGHMC has its own."""
+        if self.per_chain is None:
+            return (float(lrs[0]), float(lrs[1])), None, False
+        if rows is not None:
+            return None, rows, False
+        l0, l1 = (np.broadcast_to(np.asarray(v, dtype=np.float64), (self.K,)) for v in lrs)
+        return None, self._upload_rows(self.chain_rows(l0, l1)), True
+
+    def _health_sweep(self, grads, a, kw):
+        """One kernels.chain_stats launch over the raw gradients of this step
+        (before any clip), theta and the momentum as they stand before the
+        update, accumulated on the device; no host sync.  Returns update's
+        keywords (with the per_chain rows formed here, so that update does not
+        upload them again)."""
+        st = self.state
+        st.use_grads(grads)
+        seg, nseg, idx = st.stat_segments()
+        lr, rows, formed = self._health_lr(*a, **kw)
+        if formed:
+            kw = dict(kw, rows=rows)
+        h = self._health
+        if h is None:
+            h = self._health = [torch.zeros(self.K, nseg, len(L.STATS_SUMS), dtype=torch.float64,
+                                            device=st.device),
+                                K.chain_stats_workspace(self.K, nseg, st.device), 0, idx,
+                                K.stats_blocks_per_chain(st.n1, self.K, st.device)]
+        elif h[3] != idx:
+            raise ValueError("health: the set of tensors that have a gradient changed between "
+                             "accumulated steps (call health() before changing it)")
+        K.chain_stats(seg, nseg, self.K, st.chain_groups, st.theta, h[0], mom=st.mom,
+                      prior_mean=st.prior, lr=lr, lr_table=rows, lr_row_stride=PC.COLUMNS,
+                      accumulate=True, workspace=h[1], blocks_per_chain=h[4])
+        h[2] += 1
+        return kw
+
+    def _health_temperatures(self, acc, steps, numel):
+        """The temperature entries of `health()`; none here (see its docstring)."""
+        return {}
+
+    def health(self, reset=True):
+        """Per-chain, per-tensor health over the steps the statistics sweep
+        ran at (health_every=m: the steps with step_count % m == 0; the sweep
+        sits between gradients() and update(), so gradient, theta and momentum
+        are taken at the same theta, the gradient before any clip).  One host
+        read.  Returns `steps` (sweeps accumulated), `names` and `numel` of the
+        T tensors that have a gradient, `sums` (the raw [K, T, 6] accumulator:
+        G2, V2, D2, DG, VG, V2L of include/bdl_stats.h) and [K, T] float64 arrays:
+        grad_rms = sqrt(G2 / (steps * numel)), mom_rms, dist_rms (the distance
+        from the prior mean; from 0 where the sampler has none) and
+        grad_mom_cos = VG / sqrt(G2 * V2), the cosine between gradient and
+        momentum (bayesdll_amd.health).
+
+        StackedCSGHMC adds t_kin and t_conf [K, T], the kinetic and
+        configurational temperature of every (chain, tensor) in units of the
+        temperature the sampler's own noise scale nd * sqrt(2 alpha lr) / N
+        stands for if injected every step, and their per-chain aggregates
+        t_kin_chain / t_conf_chain [K]; under per_chain chain k's values use
+        chain k's momentum_decay, nd, Ninflate and prior_sig.  Both are 1 for
+        a stationary chain on a quadratic in the small-step limit and rise
+        with the step size and with gradient noise.  The reference adds noise
+        only on the thinned sample steps, so values well below 1 are expected
+        with thin > 1 and during exploration; the numbers compare chains and
+        layers, they are not a pass / fail.  The other samplers return the rms
+        table only: their `mom` is not a physical momentum (SGD's buffer, the
+        Adam samplers' preconditioned v), and StackedSGHMC's friction momentum
+        lives in lr-scaled gradient units whose temperature is not defined
+        here.
+
+        reset: empty the accumulators afterwards.  They are not part of
+        state_dict / checkpoints and restart empty after load_ckpt."""
+        from . import health as H
+        if not self.health_every:
+            raise ValueError("health: this sampler was built with health_every=0")
+        st, h = self.state, self._health
+        if h is None:
+            idx = tuple(i for i, rg in enumerate(st.requires_grad) if rg)
+            acc, steps = np.zeros((self.K, len(idx), len(L.STATS_SUMS))), 0
+        else:
+            acc, steps, idx = h[0].cpu().numpy(), h[2], h[3]
+            if reset:
+                h[0].zero_()
+                h[2] = 0
+        numel = [st.numels[i] for i in idx]
+        out = {"steps": int(steps), "names": [st.names[i] for i in idx], "numel": numel,
+               "sums": acc}
+        out.update(H.rms_table(acc, steps, numel))
+        out.update(self._health_temperatures(acc, steps, numel))
+        return out
+
+    def _report_health(self, ep, rec, log):
+        """One log line per chain and rec["health"] from `health()` (run.py
+        --health): the chain's aggregate temperatures and its hottest tensor
+        (cSGHMC), else its largest gradient rms."""
+        d = self.health()
+        keep = ("grad_rms", "mom_rms", "dist_rms", "grad_mom_cos", "t_kin", "t_conf",
+                "t_kin_chain", "t_conf_chain")
+        rec["health"] = {"steps": d["steps"], "names": d["names"],
+                         **{k: d[k].tolist() for k in keep if k in d}}
+        if d["steps"] == 0:
+            log(f"(Epoch {ep}) health: no step accumulated")
+            return
+        for k in range(self.K):
+            who = f"(Epoch {ep}) chain {self.chain0 + k}"
+            if self.per_chain is not None:
+                who += f": {PC.describe(self.per_chain, self.swept, k)}"
+            if "t_kin" in d:
+                hot = np.where(np.isfinite(d["t_kin"][k]), d["t_kin"][k], -np.inf)
+                t = int(np.argmax(hot))
+                log(f"{who}: t_kin_chain = {d['t_kin_chain'][k]:.4g}, t_conf_chain = "
+                    f"{d['t_conf_chain'][k]:.4g} over {d['steps']} steps; hottest tensor "
+                    f"{d['names'][t]} (t_kin = {d['t_kin'][k, t]:.4g})")
+            else:
+                t = int(np.argmax(np.nan_to_num(d["grad_rms"][k], nan=-np.inf)))
+                log(f"{who}: largest gradient rms {d['grad_rms'][k, t]:.4g} in {d['names'][t]} "
+                    f"over {d['steps']} steps")
 
     def _clip_chains(self):
         """clip_grad_norm_(self.clip_grad) of every chain by the norm of its
@@ -684,6 +844,9 @@ class _StackedSampler:
         self.chain0, self.seed = d["chain0"], d["seed"]
         self.step_count, self.draws = d["step_count"], d["draws"]
         self._load_extra_state(d)
+        if self._health is not None:  # not checkpointed: the accumulators restart empty
+            self._health[0].zero_()
+            self._health[2] = 0
         return d
 
     def train(self, train_loader, test_loader=None, start_epoch=0):
@@ -717,6 +880,8 @@ class _StackedSampler:
                     self._report_chains(ep, rec, test_loader, log)
                 if getattr(self.args, "rhat", False):  # opt-in (run.py --rhat)
                     self._report_rhat(ep, rec, log)
+            if self.health_every:  # opt-in (run.py --health)
+                self._report_health(ep, rec, log)
             hist.append(rec)
         return hist
 
@@ -782,6 +947,24 @@ class StackedCSGHMC(_StackedSampler):
         every batch, expanded on the host."""
         lrs = np.stack([PC.cyclical_lrs(self.scheds, epoch, b, bpe) for b in range(bpe)])
         return self.chain_rows(lrs)
+
+    def _health_lr(self, lr, should_sample=False, collect=None, rows=None):
+        if self.per_chain is None:
+            return (float(lr), float(lr * (self.args.lr_head / self.args.lr))), None, False
+        if rows is not None:
+            return None, rows, False
+        lr_k = np.broadcast_to(np.asarray(lr, dtype=np.float64), (self.K,))
+        return None, self._upload_rows(self.chain_rows(lr_k)), True
+
+    def _health_temperatures(self, acc, steps, numel):
+        from . import health as H
+        pc, ND = self.per_chain, self.args.ND
+        if pc is None:
+            return H.temperatures(acc, steps, numel, alpha=self.momentum_decay, nd=self.nd,
+                                  N=ND * self.Ninflate, prior_sig=self.prior_sig)
+        return H.temperatures(acc, steps, numel, alpha=pc["momentum_decay"], nd=pc["nd"],
+                              N=np.asarray([ND * float(v) for v in pc["Ninflate"]]),
+                              prior_sig=pc["prior_sig"])
 
     def update(self, grads, lr, should_sample=False, collect=None, rows=None):
         """The fused launch over all chains for given gradients (step's second
