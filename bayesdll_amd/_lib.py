@@ -224,6 +224,43 @@ STATS_EXPORTS = {
     "bdl_chain_stats": (C.c_int, [C.POINTER(StatsArgs), C.c_void_p]),
 }
 
+
+
+class EssFoldArgs(C.Structure):
+    """include/bdl_ess.h bdl_ess_fold_args."""
+    _fields_ = [("theta", _fp), ("bsum", _fp), ("smean", _fp), ("sM2", _fp), ("bM2", _fp),
+                ("n", C.c_int64), ("chain_groups", C.c_uint64), ("sample", C.c_int64),
+                ("batch", C.c_int64), ("chains", C.c_int32), ("flags", C.c_int32),
+                ("fs", C.c_float), ("fb", C.c_float), ("c", C.c_float),
+                ("grid_blocks", C.c_int32)]
+
+
+class EssSummary(C.Structure):
+    """include/bdl_ess.h bdl_ess_summary (the start of the report's workspace)."""
+    _fields_ = [("n_eval", C.c_int64), ("n_degenerate", C.c_int64), ("n_nonfinite", C.c_int64),
+                ("argmin", C.c_int64), ("n_below", C.c_int64 * 3), ("ess_sum", C.c_double),
+                ("ess_min", C.c_float), ("pad", C.c_float)]
+
+
+class EssArgs(C.Structure):
+    """include/bdl_ess.h bdl_chain_ess_args."""
+    _fields_ = [("sM2", _fp), ("bM2", _fp), ("ess", _fp), ("mcse", _fp), ("workspace", _fp),
+                ("n", C.c_int64), ("chain_groups", C.c_uint64), ("samples", C.c_int64),
+                ("batches", C.c_int64), ("chains", C.c_int32), ("grid_blocks", C.c_int32),
+                ("thresholds", C.c_float * 3), ("pad0", C.c_int32)]
+
+
+# bdl_ess_flag
+ESS_FIRST_SAMPLE, ESS_FIRST_IN_BATCH, ESS_CLOSE, ESS_FIRST_BATCH = 0x1, 0x2, 0x4, 0x8
+ESS_MAX_COUNT, ESS_MAX_CHAINS, ESS_MAX_GRID = 1 << 24, 65535, 2048
+
+# include/bdl_ess.h: additive to the ABI, as DIAG_EXPORTS
+ESS_EXPORTS = {
+    "bdl_chain_ess_fold": (C.c_int, [C.POINTER(EssFoldArgs), C.c_void_p]),
+    "bdl_chain_ess_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "bdl_chain_ess": (C.c_int, [C.POINTER(EssArgs), C.c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -244,7 +281,8 @@ def lib():
             for name, (res, argt) in (list(EXPORTS.items()) + list(DIAG_EXPORTS.items())
                                       + list(CLIP_EXPORTS.items())
                                       + list(CHAIN_STEP_EXPORTS.items())
-                                      + list(STATS_EXPORTS.items())):
+                                      + list(STATS_EXPORTS.items())
+                                      + list(ESS_EXPORTS.items())):
                 fn = getattr(h, name)
                 fn.restype = res
                 fn.argtypes = argt

@@ -14,6 +14,7 @@ import os
 import torch
 
 from . import _lib as L
+from . import ess as E
 
 # Scalar-division rounding: "recip" = x * fl(1/s), what torch's HIP kernels do
 # for a tensor / Python-scalar division (so a chain is bit-compatible with the
@@ -477,6 +478,146 @@ def chain_diag(mom1, mom2, *, chains, chain_groups, n, var_mode, ratio, count, v
     ev = torch.cuda.Event()
     ev.record(torch.cuda.current_stream(dev))
     return DiagResult(outs, snap, ev, thresholds)
+
+
+ESS_OUTPUTS = ("ess", "mcse")
+ESS_VECTORS = ("bsum", "smean", "sM2", "bM2")
+_ESS_WS = {}  # device index -> workspace (summary + per-workgroup partials)
+
+
+def ess_fold_bytes_per_elem(flags):
+    """Algorithmic HBM bytes per element of one ess_fold with these
+    bdl_ess_flag bits: 24-32 outside a component's first sample."""
+    return E.fold_bytes_per_elem(int(flags))
+
+
+def ess_bytes_per_elem(chains, outputs):
+    """Algorithmic HBM bytes per evaluated element of one chain_ess sweep."""
+    return E.report_bytes_per_elem(chains, outputs)
+
+
+def _ess_layout(what, vectors, chains, chain_groups, n):
+    chains, chain_groups, n = int(chains), int(chain_groups), int(n)
+    if not 1 <= chains <= L.ESS_MAX_CHAINS:
+        raise ValueError(f"{what}: 1 <= chains <= {L.ESS_MAX_CHAINS} is required")
+    if not 1 <= n <= 4 * chain_groups:
+        raise ValueError(f"{what}: 1 <= n <= 4 * chain_groups is required")
+    need = 4 * chain_groups * (chains - 1) + n
+    dev = None
+    for nm, t in vectors:
+        L.require_hip(t, nm)
+        if not t.is_contiguous() or t.numel() < need:
+            raise ValueError(f"{what}: {nm} must be contiguous with at least {need} elements")
+        if dev is not None and t.device != dev:
+            raise ValueError(f"{what}: all vectors must be on one device")
+        dev = t.device
+    return chains, chain_groups, n, dev
+
+
+def ess_fold(theta, bsum, smean, sM2, bM2, *, chains, chain_groups, n, sample, batch,
+             grid_blocks=0):
+    """Fold one collected sample of every chain into the batch-means
+    accumulators (bdl_chain_ess_fold, include/bdl_ess.h): `sample` is its
+    1-based index in the component, `batch` the batch length b; flags and
+    scalars come from ess.fold_plan.  All vectors are stacked like theta
+    (chain k, element j at 4*chain_groups*k + j); bsum may be None at b == 1.
+    One launch on the current stream, no host synchronisation.  Values never
+    depend on grid_blocks (workgroups per chain, 0: default).  Returns the
+    flags."""
+    flags, fs, fb, c = E.fold_plan(sample, batch)
+    vecs = [("theta", theta), ("smean", smean), ("sM2", sM2), ("bM2", bM2)]
+    if int(batch) > 1:
+        if bsum is None:
+            raise ValueError("ess_fold: bsum is required with batch > 1")
+        vecs.append(("bsum", bsum))
+    chains, chain_groups, n, dev = _ess_layout("ess_fold", vecs, chains, chain_groups, n)
+    a = L.EssFoldArgs()
+    a.theta, a.smean, a.sM2, a.bM2 = (t.data_ptr() for t in (theta, smean, sM2, bM2))
+    a.bsum = bsum.data_ptr() if int(batch) > 1 else None
+    a.n, a.chain_groups, a.chains = n, chain_groups, chains
+    a.sample, a.batch, a.flags = int(sample), int(batch), flags
+    a.fs, a.fb, a.c = fs, fb, c
+    a.grid_blocks = int(grid_blocks)
+    L.check(L.lib().bdl_chain_ess_fold(a, L.current_stream_handle(dev)), "bdl_chain_ess_fold")
+    return flags
+
+
+def chain_ess_workspace(device):
+    """The report's device scratch (summary + per-workgroup partials), one per device."""
+    dev = torch.device(device)
+    ws = _ESS_WS.get(dev.index)
+    if ws is None:
+        nbytes = int(L.lib().bdl_chain_ess_workspace_bytes(1))
+        ws = _ESS_WS[dev.index] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    return ws
+
+
+class EssResult(dict):
+    """chain_ess's result: the requested output tensors by name and `summary`
+    (the raw fields of bdl_ess_summary plus `thresholds`), read lazily — the
+    first access copies the struct from the device (one D2H copy, one sync of
+    the launch stream) and is cached."""
+
+    def __init__(self, outs, ws, event, thresholds):
+        super().__init__(outs)
+        self._ws, self._event, self._thresholds, self._summary = ws, event, thresholds, None
+
+    def __missing__(self, key):
+        if key != "summary":
+            raise KeyError(key)
+        return self.summary
+
+    @property
+    def summary(self):
+        if self._summary is None:
+            self._event.synchronize()
+            s = L.EssSummary.from_buffer_copy(self._ws.cpu().numpy().tobytes())
+            self._summary = {
+                "n_eval": int(s.n_eval), "n_degenerate": int(s.n_degenerate),
+                "n_nonfinite": int(s.n_nonfinite), "argmin": int(s.argmin),
+                "n_below": [int(v) for v in s.n_below], "ess_sum": float(s.ess_sum),
+                "ess_min": float(s.ess_min), "thresholds": list(self._thresholds)}
+            self._ws = None
+        return self._summary
+
+
+def chain_ess(sM2, bM2, *, chains, chain_groups, n, samples, batches,
+              thresholds=E.DEFAULT_THRESHOLDS, want=(), grid_blocks=0):
+    """Batch-means effective sample size of `chains` stacked chains
+    (bdl_chain_ess, include/bdl_ess.h) from the accumulators ess_fold keeps:
+    samples = S folded per chain, batches = nb closed.  chains = 1 on one
+    chain's slice reports that chain alone.  want: any of ESS_OUTPUTS — each an
+    [n] tensor in the result; result["summary"] is read on first access.  One
+    sweep and a one-workgroup combine on the current stream, no host
+    synchronisation here.  Values never depend on grid_blocks (workgroups of
+    the sweep, 0: default)."""
+    samples, batches = int(samples), int(batches)
+    if samples < 2 or batches < 2:
+        raise ValueError(f"chain_ess: at least 2 samples and 2 closed batches are required "
+                         f"(samples = {samples}, batches = {batches})")
+    want = tuple(want)
+    thresholds = E.thresholds(thresholds)
+    if any(w not in ESS_OUTPUTS for w in want):
+        raise ValueError(f"chain_ess: want from {ESS_OUTPUTS}")
+    chains, chain_groups, n, dev = _ess_layout("chain_ess", (("sM2", sM2), ("bM2", bM2)), chains,
+                                               chain_groups, n)
+    ws = chain_ess_workspace(dev)
+    outs = {w: torch.empty(n, dtype=torch.float32, device=dev) for w in want}
+    a = L.EssArgs()
+    a.sM2, a.bM2 = sM2.data_ptr(), bM2.data_ptr()
+    a.ess, a.mcse = (outs[w].data_ptr() if w in outs else None for w in ESS_OUTPUTS)
+    a.workspace = ws.data_ptr()
+    a.n, a.chain_groups, a.chains = n, chain_groups, chains
+    a.samples, a.batches = samples, batches
+    for i, t in enumerate(thresholds):
+        a.thresholds[i] = t
+    a.grid_blocks = int(grid_blocks)
+    L.check(L.lib().bdl_chain_ess(a, L.current_stream_handle(dev)), "bdl_chain_ess")
+    # the struct leaves the shared workspace in stream order (as chain_diag's)
+    snap = ws[:C.sizeof(L.EssSummary)].clone()
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(dev))
+    return EssResult(outs, snap, ev, thresholds)
 
 
 _CLIP_WS = {}  # (device index, chains) -> workspace ((norm, coef) per chain + partials)

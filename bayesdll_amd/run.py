@@ -123,7 +123,22 @@ def build_parser():
                          "and log every chain's health after each epoch: kinetic and "
                          "configurational temperature and the hottest tensor (csghmc), the "
                          "largest gradient rms otherwise; works with --sweep")
+    ap.add_argument("--ess", type=int, default=0, metavar="B",
+                    help="with --stacked_chains >= 1: fold every collected sample into "
+                         "batch-means accumulators (batches of B samples) and log the effective "
+                         "sample size of the latest component at every evaluation (stacked "
+                         "ess()); per chain with --sweep")
     return ap
+
+
+def check_ess(ap, args):
+    """--ess B needs stacked chains and B >= 0 (ap.error otherwise)."""
+    if args.ess < 0:
+        ap.error("--ess: B must be >= 0")
+    if args.ess and args.stacked_chains < 1:
+        ap.error("--ess folds the stacked chains' collected samples: it needs "
+                 "--stacked_chains >= 1")
+    return args.ess
 
 
 def check_health(ap, args):
@@ -218,6 +233,7 @@ def main(argv=None):
         ap.error("--rhat compares the chains of one device: it needs --stacked_chains >= 2")
     sweep = parse_sweep(ap, args)
     check_health(ap, args)
+    check_ess(ap, args)
     from . import chains
     rank, world, device = chains.init_chains()
     if device.type != "cuda":
@@ -282,6 +298,8 @@ def main(argv=None):
         kw = {} if sweep is None else {"per_chain": sweep}
         if args.health:
             kw["health_every"] = args.health
+        if args.ess:
+            kw["ess_batch"] = args.ess
         S = cls(net, args.stacked_chains, args, logger=logger, init="reinit", graph=args.graph,
                 net0=net0, **kw)
         logger.info(f"{args.stacked_chains} stacked chains on this device "

@@ -46,6 +46,7 @@ import torch.nn.functional as F
 from torch.func import functional_call, grad_and_value, vmap
 
 from . import _lib as L
+from . import ess as ESS
 from . import kernels as K
 from . import per_chain as PC
 from ._base import no_gc
@@ -372,12 +373,17 @@ class _StackedSampler:
 
     def __init__(self, net, K_, args, *, chain0=None, seed=None, init="copy", criterion=None,
                  per_chain_batches=False, logger=None, graph=None, net0=None, per_chain=None,
-                 health_every=0):
+                 health_every=0, ess_batch=0):
         from . import chains
         from ._base import default_graph
         self._init_per_chain(per_chain, K_, args)
         if int(health_every) != health_every or int(health_every) < 0:
             raise ValueError(f"health_every must be an integer >= 0 (got {health_every!r})")
+        # batch length b of the batch-means ESS accumulators every collected
+        # sample is folded into after `update` (0: never; then step() is
+        # unchanged and nothing is allocated)
+        self.ess_batch = ESS.check_batch(ess_batch)
+        self._ess = None  # [{bsum, smean, sM2, bM2}, samples folded into the latest component]
         # every m-th step the statistics sweep runs between gradients() and
         # update() (0: never; then step() is unchanged and nothing is allocated)
         self.health_every = int(health_every)
@@ -492,7 +498,101 @@ class _StackedSampler:
         if self.health_every and self.step_count % self.health_every == 0:
             kw = self._health_sweep(grads, a, kw)
         self.update(grads, *a, **kw)
+        if self.ess_batch and kw.get("collect") is not None:
+            self._ess_fold(kw["collect"][0])
         return loss, out
+
+    # ------------------------------------------------------------------ ess
+    def _ess_fold(self, kind):
+        """Fold the theta this step's collect just accumulated into the
+        batch-means accumulators (kernels.ess_fold: one launch, no host sync).
+        An init collect opens a new component: the counters restart, so the
+        accumulators always describe the latest component and a batch never
+        straddles two (an open partial batch is dropped)."""
+        st, e = self.state, self._ess
+        if e is None:
+            names = K.ESS_VECTORS if self.ess_batch > 1 else K.ESS_VECTORS[1:]
+            e = self._ess = [{nm: torch.zeros_like(st.theta) for nm in names}, 0]
+        if kind in (L.COLLECT_WELFORD_INIT, L.COLLECT_MEAN_INIT):
+            e[1] = 0
+        v = e[0]
+        K.ess_fold(st.theta, v.get("bsum"), v["smean"], v["sM2"], v["bM2"], chains=self.K,
+                   chain_groups=st.chain_groups, n=st.n1, sample=e[1] + 1, batch=self.ess_batch)
+        e[1] += 1
+
+    def ess(self, *, by_chain=False, ess=False, mcse=False, thresholds=None):
+        """How many independent samples do the collected samples of the latest
+        component stand for?  The batch-means effective sample size per
+        element, pooled over the K chains the way R-hat pools the within-chain
+        variance, from accumulators every collected sample was folded into
+        (ess_batch = b: batches of b consecutive samples; bayesdll_amd.ess,
+        include/bdl_ess.h) in one fused sweep (kernels.chain_ess).  Returns
+        the summary (n_eval, n_degenerate, n_nonfinite, ess_min, argmin and
+        its parameter name, ess_mean, n_below / share_below the thresholds —
+        default 100 / 400 / 1000 —, samples folded and batches closed per
+        chain, batch, chains, component) plus, when asked for, the [n1]
+        tensors `ess` and `mcse` (the Monte Carlo standard error of one chain's
+        mean from the pooled batch variance; the mean over all K chains has
+        mcse / sqrt(K)).  by_chain=True: a list of K such results, chain k's from its own
+        accumulators alone (K launches) — the only form under per_chain
+        hyperparameters, whose chains target different posteriors.
+
+        The accumulators count true samples (no double count, no burn-in
+        seed), restart at a component's init collect, are no part of
+        state_dict / checkpoints and restart empty after load_ckpt.  Reads the
+        accumulators only: nothing the sampler owns is written."""
+        if not self.ess_batch:
+            raise ValueError("ess: this sampler was built with ess_batch=0")
+        if self.per_chain is not None and not by_chain:
+            raise ValueError("ess: this sampler runs per_chain hyperparameters; the pooled ESS "
+                             "pools chains that target ONE posterior, and these chains target "
+                             "different ones (ask for by_chain=True)")
+        thr = ESS.thresholds(thresholds)
+        S_, nb = ESS.check_report(0 if self._ess is None else self._ess[1], self.ess_batch)
+        st, v = self.state, self._ess[0]
+        want = (("ess",) if ess else ()) + (("mcse",) if mcse else ())
+        comp = self._latest_component()
+
+        def report(sl, chains):
+            res = K.chain_ess(v["sM2"][sl:], v["bM2"][sl:], chains=chains,
+                              chain_groups=st.chain_groups, n=st.n1, samples=S_, batches=nb,
+                              thresholds=thr, want=want)
+            return res
+
+        def finish(res, chains):
+            out = ESS.summary_dict(res.summary, thr, samples=S_, batches=nb,
+                                   batch=self.ess_batch, chains=chains)
+            out["component"] = comp
+            out["argmin_param"] = self.param_of(out["argmin"]) if out["argmin"] >= 0 else None
+            out.update({w: res[w] for w in want})
+            return out
+
+        if not by_chain:
+            return finish(report(0, self.K), self.K)
+        launched = [report(k * st.stride, 1) for k in range(self.K)]  # K launches, then one wait
+        return [finish(r, 1) for r in launched]
+
+    def _report_ess(self, ep, rec, log):
+        """One log line (one per chain under per_chain) and rec["ess"] from
+        `ess()` (run.py --ess); an evaluation that comes before two batches are
+        closed says so and goes on."""
+        try:
+            d = self.ess(by_chain=self.per_chain is not None)
+        except ValueError as e:
+            log(f"(Epoch {ep}) ESS: {e}")
+            return
+        rec["ess"] = d
+        for k, r in enumerate(d if isinstance(d, list) else [d]):
+            who = f"over {self.K} chains"
+            if isinstance(d, list):
+                who = f"chain {self.chain0 + k}: {PC.describe(self.per_chain, self.swept, k)}"
+            shares = ", ".join(f"< {t:g}: {100 * s:.1f} %"
+                               for t, s in zip(r["thresholds"], r["share_below"]))
+            log(f"(Epoch {ep}) ESS {who}, component {r['component']} ({r['samples']} samples "
+                f"each, {r['batches']} batches of {r['batch']}): min = {r['ess_min']:.1f} "
+                f"({r['argmin_param']}), mean = {r['ess_mean']:.1f}, {shares}; "
+                f"{r['n_eval']} evaluated, {r['n_degenerate']} degenerate, "
+                f"{r['n_nonfinite']} non-finite")
 
     # --------------------------------------------------------------- health
     def _health_lr(self, lrs, collect=None, rows=None):
@@ -847,6 +947,8 @@ class _StackedSampler:
         if self._health is not None:  # not checkpointed: the accumulators restart empty
             self._health[0].zero_()
             self._health[2] = 0
+        if self._ess is not None:     # nor are these: the next fold is a first sample
+            self._ess[1] = 0
         return d
 
     def train(self, train_loader, test_loader=None, start_epoch=0):
@@ -880,6 +982,8 @@ class _StackedSampler:
                     self._report_chains(ep, rec, test_loader, log)
                 if getattr(self.args, "rhat", False):  # opt-in (run.py --rhat)
                     self._report_rhat(ep, rec, log)
+                if self.ess_batch:  # opt-in (run.py --ess)
+                    self._report_ess(ep, rec, log)
             if self.health_every:  # opt-in (run.py --health)
                 self._report_health(ep, rec, log)
             hist.append(rec)
