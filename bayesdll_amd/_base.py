@@ -105,6 +105,21 @@ def default_overlap():
 OVERLAP_BUCKET_ELEMS = int(float(os.environ.get("BDL_OVERLAP_BUCKET_MB", "64")) * (1 << 18))
 
 
+def default_compute_dtype():
+    """BDL_COMPUTE_DTYPE=bf16: the network computes in bf16 over an fp32 chain
+    state (include/bdl_lowp.h); fp32 end to end otherwise."""
+    from .flat import check_compute_dtype
+    return check_compute_dtype(os.environ.get("BDL_COMPUTE_DTYPE") or None)
+
+
+def refuse_compute_dtype(compute_dtype, what):
+    """Samplers without a bf16 form name the limit."""
+    from .flat import check_compute_dtype
+    if check_compute_dtype(compute_dtype) is not None:
+        raise ValueError(f"bayesdll_amd: compute_dtype=bf16 is not supported by {what}; "
+                         "the bf16 step covers csghmc, csghmc_fs, sghmc, sgld and unclipped csgld")
+
+
 def default_chain():
     """Chain id = process rank when torch.distributed is initialised."""
     from . import chains
@@ -141,7 +156,8 @@ class FusedModelBase(nn.Module):
         self._graph_bound = None  # the graph whose static gradients the params' .grad hold
         self.graph_captures = 0   # captures so far (one per input shape, unless released)
         self.overlap = default_overlap()
-        self._ovl = None          # per-backward bucket bookkeeping while overlapping
+        self.compute_dtype = default_compute_dtype()  # None (fp32) or torch.bfloat16
+        self._ovl = None         # per-backward bucket bookkeeping while overlapping
         self._ovl_plan = None
         self._ovl_hooks = None
         self._side = None
@@ -160,11 +176,15 @@ class FusedModelBase(nn.Module):
             if self.noise_mode not in NOISE_MODES:
                 raise ValueError(f"noise_mode must be one of {NOISE_MODES}")
             from . import kernels as K
+            from .flat import check_compute_dtype
+            cdt = check_compute_dtype(self.compute_dtype)
+            if cdt is not None:
+                self.check_lowp()
             self._state = FlatState(net, net0, readout_name=getattr(net, "readout_name", None),
                                     bias=getattr(self, "bias", "informative"),
                                     need_prior=self.need_prior, need_mom=self.need_mom,
                                     need_noise=self.noise_mode != "philox",
-                                    extra=self.extra_vectors)
+                                    extra=self.extra_vectors, compute_dtype=cdt)
             self._state_net = net
             steps_timed = int(os.environ.get("BDL_STEP_TIMING", "0") or 0)
             if steps_timed > 0:  # sampled update timing, logged once per epoch
@@ -175,8 +195,38 @@ class FusedModelBase(nn.Module):
             # vectors it writes restored after every candidate
             # (kernels.request_state_tuning)
             self._state.launch_cfg = self._state.collect_cfg = self._state.init_cfg = None
-            K.request_state_tuning(self._state, self.tune_method)
+            if cdt is None:  # the bf16 step launches with its default geometry
+                K.request_state_tuning(self._state, self.tune_method)
         return self._state
+
+    def refuse_lowp_grad_contract(self, sgd, clip_grad=None):
+        """bf16 compute: the reference's gradient-only contract (no `sgd`: the
+        caller steps) and the clipped step have no bf16 form; refused before
+        the state is built or the network touched."""
+        from .flat import check_compute_dtype
+        if check_compute_dtype(self.compute_dtype) is None:
+            return
+        if sgd is None:
+            raise ValueError("bayesdll_amd: compute_dtype=bf16 does not support the *_GRAD "
+                             "contract (Model.forward without `sgd`: the caller steps); pass the "
+                             "FusedSGD so that the fused step updates theta and its shadow")
+        if clip_grad is not None:
+            raise ValueError("bayesdll_amd: compute_dtype=bf16 does not support clip_grad "
+                             "(the clipped cSGLD step has no bf16 form)")
+
+    lowp_ok = False  # does this sampler step through kernels.sgmcmc_step alone?
+
+    def check_lowp(self):
+        """bf16 compute: what this sampler or its configuration does not
+        cover, refused before the state is built."""
+        if not self.lowp_ok:
+            refuse_compute_dtype(self.compute_dtype, type(self).__module__)
+        if self.graph:
+            raise ValueError("bayesdll_amd: compute_dtype=bf16 does not support graph mode "
+                             "(BDL_GRAPH=1): the capture path binds fp32 static gradients")
+        if self.overlap:
+            raise ValueError("bayesdll_amd: compute_dtype=bf16 does not support the overlapped "
+                             "update (BDL_OVERLAP=1)")
 
     @property
     def flat(self):
@@ -184,6 +234,14 @@ class FusedModelBase(nn.Module):
 
     # ----------------------------------------------------------- fwd/bwd
     def forward_backward(self, st, net, x, y, criterion):
+        if st.compute_dtype is not None:
+            # bf16 network over the shadow; the loss and the returned logits in fp32
+            out = net(x.to(st.compute_dtype) if x.is_floating_point() else x)
+            loss = criterion(out.float(), y)
+            st.zero_grad()
+            loss.backward()
+            st.sync_grads()
+            return loss, out.float()
         if self.graph and x.is_cuda and y.is_cuda and torch.is_grad_enabled():
             got = self._graphed_forward_backward(st, net, x, y, criterion)
             if got is not None:

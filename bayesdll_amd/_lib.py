@@ -261,6 +261,37 @@ ESS_EXPORTS = {
     "bdl_chain_ess": (C.c_int, [C.POINTER(EssArgs), C.c_void_p]),
 }
 
+
+
+class LowpArgs(C.Structure):
+    """include/bdl_lowp.h bdl_lowp_args."""
+    _fields_ = [
+        ("theta", _fp), ("grad", _fp), ("mom", _fp), ("prior_mean", _fp), ("noise", _fp),
+        ("mom1", _fp), ("mom2", _fp), ("shadow", _fp), ("runs", _fp), ("grad_base", _fp),
+        ("nonfinite", _fp), ("n", C.c_int64),
+        ("nruns", C.c_int32), ("method", C.c_int32), ("noise_mode", C.c_int32),
+        ("collect", C.c_int32), ("flags", C.c_int32), ("blocks", C.c_int32),
+        ("unroll", C.c_int32), ("pad0", C.c_int32),
+        ("lr", C.c_float * 2), ("noise_scale", C.c_float * 2),
+        ("one_minus_alpha", C.c_float), ("prior_sig", C.c_float), ("sigma2", C.c_float),
+        ("n_data", C.c_float), ("mu", C.c_float), ("collect_a", C.c_float),
+        ("collect_b", C.c_float), ("inv_sigma2", C.c_float), ("inv_n_data", C.c_float),
+        ("inv_collect_a", C.c_float), ("inv_collect_b", C.c_float), ("pad1", C.c_float),
+        ("seed", C.c_uint64), ("chain", C.c_uint64), ("step", C.c_uint64),
+        ("philox_offset", C.c_uint64), ("chain_groups", C.c_uint64),
+    ]
+
+
+LOWP_MAX_BLOCKS = 65536
+LOWP_UNROLLS = (1, 2, 4)
+
+# include/bdl_lowp.h: additive to the ABI, as DIAG_EXPORTS
+LOWP_EXPORTS = {
+    "bdl_lowp_step": (C.c_int, [C.POINTER(LowpArgs), C.c_void_p]),
+    "bdl_lowp_shadow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64,
+                                  C.c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -282,7 +313,8 @@ def lib():
                                       + list(CLIP_EXPORTS.items())
                                       + list(CHAIN_STEP_EXPORTS.items())
                                       + list(STATS_EXPORTS.items())
-                                      + list(ESS_EXPORTS.items())):
+                                      + list(ESS_EXPORTS.items())
+                                      + list(LOWP_EXPORTS.items())):
                 fn = getattr(h, name)
                 fn.restype = res
                 fn.argtypes = argt

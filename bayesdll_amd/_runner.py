@@ -64,6 +64,46 @@ class PosteriorDraw:
         self.count += 1
 
 
+def set_compute_dtype(runner, args):
+    """args.compute_dtype ("bf16" / torch.bfloat16; None or "fp32": fp32 end
+    to end) onto the Runner's Model; what the bf16 step does not cover is
+    refused here, before any state is built."""
+    from .flat import check_compute_dtype
+    model = runner.model
+    if getattr(args, "compute_dtype", None) is not None:
+        model.compute_dtype = check_compute_dtype(args.compute_dtype)
+    if model.compute_dtype is None:
+        return
+    model.check_lowp()
+    if getattr(runner, "clips_gradients", False) and getattr(args, "clip_grad", None) is not None:
+        raise ValueError("bayesdll_amd: compute_dtype=bf16 does not support clip_grad (the "
+                         "clipped cSGLD step has no bf16 form)")
+
+
+def point_estimate_net(runner):
+    """The network a point estimate is scored on: runner.net, or with bf16
+    compute an fp32 evaluation copy holding the fp32 master theta (evaluation
+    stays fp32)."""
+    st = runner.model.flat
+    if st is None or st.shadow is None:
+        return runner.net
+    draw = PosteriorDraw(runner.net, "philox", 0, 0)
+    draw.load_mean(st.theta)
+    return draw.net
+
+
+def net_state_dict(runner):
+    """net.state_dict() as the checkpoints store it.  bf16 compute: the fp32
+    master values under the same names (the parameters themselves are bf16
+    views of the shadow), so a checkpoint holds what an fp32 run's holds."""
+    st = runner.model.flat
+    sd = runner.net.state_dict()
+    if st is None or st.shadow is None:
+        return sd
+    fp32 = dict(zip(st.names, st.views(st.theta)))
+    return type(sd)((k, fp32.get(k, v)) for k, v in sd.items())
+
+
 def defer_loss(runner):
     """Let the Runner's Model return device losses (no per-step host sync);
     BDL_SYNC_LOSS=1 restores the reference's per-step loss.item()."""
@@ -532,6 +572,7 @@ def restore_resume_state(model, st, ckpt, sgd=None):
             st.mom.copy_(rs["mom"].to(st.mom.device))
         for k, v in rs.get("extra", {}).items():
             st.extra[k].copy_(v.to(st.extra[k].device))
+    st.refresh_shadow()  # bf16 compute: the network reads theta through its shadow
     model.step_count = int(rs["step_count"])
     model.seed = int(rs["seed"])
     model.chain = int(rs["chain"])

@@ -71,6 +71,7 @@ class Runner:
             self.model.graph = bool(args.graph)
         if getattr(args, "overlap", None) is not None:
             self.model.overlap = bool(args.overlap)
+        R.set_compute_dtype(self, args)
 
         # lr holder with the reference's two param groups (body, head)
         self.optimizer = torch.optim.SGD(
@@ -221,7 +222,7 @@ class Runner:
             if last_in_cycle:
                 cycle_number = sched.get_cycle_number(epoch=ep, batch=batch_idx,
                                                       batches_per_epoch=bpe)
-                self.cycle_states[cycle_number] = copy.deepcopy(self.net.state_dict())
+                self.cycle_states[cycle_number] = copy.deepcopy(R.net_state_dict(self))
                 if cycle_number > self.current_cycle:
                     cycle_updated = True
                     self.current_cycle = cycle_number
@@ -322,6 +323,7 @@ class Model(FusedModelBase):
     need_prior = False  # Q1: theta0 never enters the csghmc update
     need_mom = True
     tune_method = "csghmc"
+    lowp_ok = True
 
     def __init__(self, ND, runner=None, prior_sig=1.0, bias="informative", momentum_decay=0.05):
         super().__init__()

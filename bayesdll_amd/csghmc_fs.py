@@ -56,9 +56,15 @@ class Runner(_CSGHMCRunner):
     def _reinitialize_network_fresh(self):
         """Cold restart: `_runner.reinit_network`, in place in the flat theta."""
         from . import _runner as R
-        R.reinit_network(self.net)
-        if self.model.flat is not None:
-            self.model.flat.check_bound()
+        st = self.model.flat
+        if st is None:
+            R.reinit_network(self.net)
+            return
+        # bf16 compute: the fresh values are drawn in fp32 into theta (the
+        # parameters bound to the master meanwhile), then the shadow refreshed
+        with st.bound_to_master():
+            R.reinit_network(self.net)
+        st.check_bound()
 
     def _cycle_completed(self, cycle_number):
         """:590-597."""
@@ -73,12 +79,12 @@ class Runner(_CSGHMCRunner):
         snapshots in the last epochs of each cycle, then the BMA evaluation."""
         args = self.args
         if val_loader is not None and (ep % 5 == 0 or ep == args.epochs - 1):
-            pl, pe = self.evaluate_point_estimate(val_loader, self.net)
+            pl, pe = self.evaluate_point_estimate(val_loader, R.point_estimate_net(self))
             self.logger.info(f"(Epoch {ep}) Point Estimate Val (Cycle {self.current_cycle} "
                              f"Mean): loss = {pl:.4f}, prediction error = {pe:.4f}")
         L = args.epochs // args.num_cycles
         if L > 0 and L - 4 < ep % L < L - 1:
-            torch.save(self.net.state_dict(),
+            torch.save(R.net_state_dict(self),
                        os.path.join(args.log_dir, f"full_samples_net_ep{ep}.pth"))
             self.evaluate_full_samples(train_loader, val_loader, test_loader,
                                        desc_prefix=f"Full Samples Epoch {ep}")

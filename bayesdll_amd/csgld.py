@@ -32,6 +32,8 @@ class Model(_SGLDModel):
 
 class Runner:
 
+    clips_gradients = True  # args.clip_grad reaches the update (refused with bf16 compute)
+
     def __init__(self, net, net0, args, logger):
         self.args = R.bind_chain_log_dir(args)
         self.diverged_epochs = []
@@ -59,6 +61,7 @@ class Runner:
             self.model.graph = bool(args.graph)
         if getattr(args, "overlap", None) is not None:
             self.model.overlap = bool(args.overlap)
+        R.set_compute_dtype(self, args)
         self.optimizer = torch.optim.SGD(
             [{"params": [p for pn, p in self.net.named_parameters()
                          if self.net.readout_name not in pn], "lr": args.lr},
@@ -199,7 +202,7 @@ class Runner:
                 cycle_number = sched.get_cycle_number(epoch=ep, batch=batch_idx,
                                                       batches_per_epoch=bpe)
                 self._cycle_end(cycle_number)
-                self.cycle_states[cycle_number] = copy.deepcopy(self.net.state_dict())
+                self.cycle_states[cycle_number] = copy.deepcopy(R.net_state_dict(self))
                 if cycle_number > self.current_cycle:
                     cycle_updated = True
                     self.current_cycle = cycle_number

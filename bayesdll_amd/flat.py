@@ -85,15 +85,53 @@ def default_grad_mode():
     return m
 
 
+COMPUTE_DTYPES = {None: None, "fp32": None, "float32": None, torch.float32: None,
+                  "bf16": torch.bfloat16, "bfloat16": torch.bfloat16,
+                  torch.bfloat16: torch.bfloat16}
+
+
+def check_compute_dtype(compute_dtype):
+    """None (fp32 end to end, the default) or torch.bfloat16 (bf16 compute
+    over an fp32 chain state, include/bdl_lowp.h)."""
+    try:
+        return COMPUTE_DTYPES[compute_dtype]
+    except (KeyError, TypeError):
+        raise ValueError(f"bayesdll_amd: compute_dtype must be fp32 or bf16, got "
+                         f"{compute_dtype!r}") from None
+
+
+def refuse_lowp_network(net, ntensors, grad_mode=None):
+    """What bf16 compute does not cover, refused before anything is allocated
+    or rebound."""
+    if (grad_mode or default_grad_mode()) != "tensor":
+        raise ValueError("bayesdll_amd: bf16 compute reads autograd's bf16 gradients in place: "
+                         "the flat gradient vector (BDL_GRAD_MODE=flat) is not supported")
+    if ntensors > MAX_TENSOR_RUNS:
+        raise ValueError(f"bayesdll_amd: bf16 compute needs one run per tensor in the kernel's "
+                         f"LDS table ({ntensors} parameter tensors > {MAX_TENSOR_RUNS}); the "
+                         "flat gradient fallback is not supported")
+    if default_grad_arena():
+        raise ValueError("bayesdll_amd: bf16 compute does not support the gradient arena "
+                         "(BDL_GRAD_ARENA=1)")
+    fbuf = [nm for nm, b in net.named_buffers() if b.is_floating_point()]
+    if fbuf:
+        raise ValueError("bayesdll_amd: bf16 compute does not support networks with "
+                         f"floating-point buffers (e.g. BatchNorm running statistics): {fbuf[:3]}")
+
+
 class FlatState:
     """Flat buffers for one chain, bound to `net`'s parameters (and, in "flat"
     gradient mode, grads)."""
 
     def __init__(self, net, net0=None, *, readout_name=None, bias="informative",
-                 need_prior=False, need_mom=True, need_noise=False, extra=(), grad_mode=None):
+                 need_prior=False, need_mom=True, need_noise=False, extra=(), grad_mode=None,
+                 compute_dtype=None):
         named = list(net.named_parameters())
         if not named:
             raise ValueError("bayesdll_amd: the network has no parameters")
+        self.compute_dtype = check_compute_dtype(compute_dtype)
+        if self.compute_dtype is not None:
+            refuse_lowp_network(net, len(named), grad_mode)
         self.names = [nm for nm, _ in named]
         self.params = [p for _, p in named]
         self.shapes = [tuple(p.shape) for p in self.params]
@@ -135,6 +173,14 @@ class FlatState:
             for p, o, k in zip(self.params, self.offsets, self.numels):
                 self.theta[o:o + k].copy_(p.data.reshape(-1))
                 p.data = self.theta[o:o + k].view(p.shape)
+        # bf16 compute: theta stays the fp32 master; the parameters become
+        # views into its bf16 shadow, which the step rewrites with theta
+        self.shadow = None
+        if self.compute_dtype is not None:
+            self.shadow = torch.empty(self.n, dtype=self.compute_dtype, device=dev)
+            self.refresh_shadow()
+            for p, o, k in zip(self.params, self.offsets, self.numels):
+                p.data = self.shadow[o:o + k].view(p.shape)
         self.grad = vecs["grad"].zero_() if self.grad_mode == "flat" else None
         self.gbase = None  # device per-run gradient bases ("tensor" mode)
         self._bind_grads()
@@ -212,6 +258,8 @@ class FlatState:
         self.extra = {nm: vecs[nm] for nm in extra}
         self.theta = vecs["theta"] if init is None else init
         self.grad_mode = "flat"
+        self.compute_dtype = None
+        self.shadow = None
         self.gbase = None
         self.arena = None
         self._grad_tables = {}
@@ -345,8 +393,9 @@ class FlatState:
                 if rg:
                     untouched.append(i)
                 continue
-            if g.dtype != torch.float32 or g.device != self.device or not g.is_contiguous():
-                g = g.to(device=self.device, dtype=torch.float32).contiguous()
+            gdt = self.compute_dtype or torch.float32
+            if g.dtype != gdt or g.device != self.device or not g.is_contiguous():
+                g = g.to(device=self.device, dtype=gdt).contiguous()
                 p.grad = g
             ptrs.append(g.data_ptr())
         key = tuple(ptrs)
@@ -363,14 +412,17 @@ class FlatState:
         attributes (+SKIP without a gradient, +GUNALIGNED when the tensor's
         base address minus 4*offset is not 16-B aligned), and the base
         address; packed as [runs (2 int64 each) | bases] in one device
-        tensor, copied from pinned memory on the current stream."""
+        tensor, copied from pinned memory on the current stream.  bf16
+        compute: 2-byte gradient elements, bases 8-B addressable
+        (include/bdl_lowp.h)."""
         nt = len(self.numels)
+        esz, align = (2, 8) if self.compute_dtype is not None else (4, 16)
         host = torch.empty(3 * nt, dtype=torch.int64).pin_memory()
         h = host.numpy()
         for i, (o, k, a, ptr) in enumerate(zip(self.offsets, self.numels, self.attrs, ptrs)):
-            base = ptr - 4 * o if ptr else 0
+            base = ptr - esz * o if ptr else 0
             at = a | (L.ATTR_SKIP if not ptr else 0)
-            if ptr and base % 16:
+            if ptr and base % align:
                 at |= L.ATTR_GUNALIGNED
             h[2 * i] = o + k
             h[2 * i + 1] = at
@@ -470,11 +522,39 @@ class FlatState:
         return not self._touched or self._touched[i]
 
     def check_bound(self):
-        """Raise if a parameter no longer aliases the flat theta buffer."""
+        """Raise if a parameter no longer aliases the flat theta buffer (bf16
+        compute: its shadow)."""
+        vec, esz = (self.theta, 4) if self.shadow is None else (self.shadow, 2)
         for nm, p, o in zip(self.names, self.params, self.offsets):
-            if p.data.data_ptr() != self.theta.data_ptr() + 4 * o:
+            if p.data.data_ptr() != vec.data_ptr() + esz * o:
                 raise RuntimeError(f"bayesdll_amd: parameter {nm!r} was re-allocated outside the "
                                    "sampler; rebuild the sampler state")
+
+    def refresh_shadow(self):
+        """bf16 compute: rewrite the shadow from theta (bdl_lowp_shadow) after
+        any write to theta outside the step — a checkpoint load, a cycle
+        restore, a cold restart.  A no-op for an fp32 state."""
+        if self.shadow is not None:
+            from . import kernels as K
+            K.lowp_shadow(self.theta, self.shadow)
+
+    @contextlib.contextmanager
+    def bound_to_master(self):
+        """bf16 compute: the parameters as fp32 views of theta for the length of
+        the block (code that rewrites them in place, e.g. a cold restart's
+        reset_parameters), then views of the shadow again, the shadow
+        refreshed from theta.  A no-op for an fp32 state."""
+        if self.shadow is None:
+            yield
+            return
+        for p, v in zip(self.params, self.views(self.theta)):
+            p.data = v
+        try:
+            yield
+        finally:
+            for p, v in zip(self.params, self.views(self.shadow)):
+                p.data = v
+            self.refresh_shadow()
 
     # --------------------------------------------------------------- views
     def views(self, vec):

@@ -194,8 +194,67 @@ def _written(state, method, *, grad_only, mom, extra=(), mom1=None, mom2=None):
     return out
 
 
+# the bf16 step's depth: two workgroups per CU x 4 groups per lane was the fastest of the
+# seven geometries timed at ViT-L/32 size (tools/lowp_timing.py)
+LOWP_UNROLL = 4
+
+
+def lowp_args(state, method, *, blocks=0, unroll=LOWP_UNROLL, **kw):
+    """bdl_lowp_args of one step over a bf16-compute state (FlatState with
+    compute_dtype=torch.bfloat16, or any object with its vectors and a bf16
+    `shadow`): the fields of _step_args, gradient and shadow in bf16."""
+    if method not in (L.CSGHMC, L.SGHMC, L.SGLD):
+        raise ValueError("bayesdll_amd: compute_dtype=bf16 covers the cSGHMC, SGHMC and SGLD "
+                         "steps; the *_GRAD contract (the caller steps) and Adam have no bf16 form")
+    if kw.get("grad_ready"):
+        raise ValueError("bayesdll_amd: the bf16 step has no GRAD_READY form (no clipped step)")
+    if kw.get("mom_buf") is not None:
+        raise ValueError("bayesdll_amd: the bf16 step takes its SGD buffer from state.mom")
+    s = _step_args(state, method, **kw)
+    a = L.LowpArgs()
+    for f in ("theta", "grad", "mom", "prior_mean", "noise", "mom1", "mom2", "runs", "grad_base",
+              "nonfinite", "n", "nruns", "method", "noise_mode", "collect", "flags",
+              "one_minus_alpha", "prior_sig", "sigma2", "n_data", "mu", "collect_a", "collect_b",
+              "inv_sigma2", "inv_n_data", "inv_collect_a", "inv_collect_b", "seed", "chain",
+              "step", "philox_offset", "chain_groups"):
+        setattr(a, f, getattr(s, f))
+    for i in range(2):
+        a.lr[i], a.noise_scale[i] = s.lr[i], s.noise_scale[i]
+    a.shadow = state.shadow.data_ptr()
+    a.blocks, a.unroll = int(blocks), int(unroll)
+    return a
+
+
+def lowp_step(state, method, **kw):
+    """One fused update over a bf16-compute state (bdl_lowp_step): bf16
+    gradients read in place, fp32 theta / momentum / moments updated exactly as
+    sgmcmc_step would on the upcast gradient, the bf16 shadow written in the
+    same sweep.  Default geometry (no per-state tuning); blocks / unroll for
+    tests and the timing tool.  Asynchronous."""
+    a = lowp_args(state, method, **kw)
+    t = getattr(state, "timer", None)
+    e0 = t.begin() if t is not None else None
+    L.check(L.lib().bdl_lowp_step(a, L.current_stream_handle(state.device)), "bdl_lowp_step")
+    if e0 is not None:
+        s = _step_args(state, method, **{k: v for k, v in kw.items()
+                                         if k not in ("blocks", "unroll")})
+        t.end(e0, alg_bytes_per_elem(s) * int(a.n))  # grad r 2 + shadow w 2 = the fp32 grad r 4
+
+
+def lowp_shadow(theta, shadow):
+    """shadow = bf16(theta), round to nearest even (bdl_lowp_shadow). Asynchronous."""
+    if shadow.dtype != torch.bfloat16 or shadow.numel() != theta.numel():
+        raise ValueError("lowp_shadow: shadow must be a bf16 tensor of theta's length")
+    L.require_hip(theta, "theta")
+    L.check(L.lib().bdl_lowp_shadow(theta.data_ptr(), shadow.data_ptr(), None, 0,
+                                    int(theta.numel()), L.current_stream_handle(theta.device)),
+            "bdl_lowp_shadow")
+
+
 def sgmcmc_step(state, method, **kw):
     """One fused update over `state` (a FlatState). Asynchronous."""
+    if getattr(state, "shadow", None) is not None:  # bf16 compute, fp32 chain state
+        return lowp_step(state, method, **kw)
     a = _step_args(state, method, **kw)
     mb = kw.get("mom_buf")
     wr = _written(state, method, grad_only=method in (L.SGHMC_GRAD, L.SGLD_GRAD),

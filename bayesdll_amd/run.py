@@ -103,6 +103,10 @@ def build_parser():
     ap.add_argument("--graph", action="store_true", help="replay forward/backward from a HIP graph")
     ap.add_argument("--overlap", action="store_true",
                     help="overlap the fused update with backward, bucket by bucket (cSGHMC)")
+    ap.add_argument("--compute_dtype", type=str, default=None, choices=["fp32", "bf16"],
+                    help="fp32 (the default, unless BDL_COMPUTE_DTYPE=bf16 is set) or bf16: the "
+                         "network computes in bf16 over an fp32 chain state (csghmc, csghmc_fs, "
+                         "sghmc, sgld, unclipped csgld; not with --stacked_chains)")
     ap.add_argument("--resume_state", action="store_true",
                     help="checkpoints carry what an exact resume needs")
     ap.add_argument("--stacked_chains", type=int, default=0,
@@ -139,6 +143,14 @@ def check_ess(ap, args):
         ap.error("--ess folds the stacked chains' collected samples: it needs "
                  "--stacked_chains >= 1")
     return args.ess
+
+
+def check_compute_dtype(ap, args):
+    """--compute_dtype bf16 is a one-chain mode (ap.error with stacked chains)."""
+    if args.compute_dtype == "bf16" and args.stacked_chains > 0:
+        ap.error("--compute_dtype bf16: the stacked samplers have no bf16 step "
+                 "(drop --stacked_chains)")
+    return args.compute_dtype
 
 
 def check_health(ap, args):
@@ -234,6 +246,7 @@ def main(argv=None):
     sweep = parse_sweep(ap, args)
     check_health(ap, args)
     check_ess(ap, args)
+    check_compute_dtype(ap, args)
     from . import chains
     rank, world, device = chains.init_chains()
     if device.type != "cuda":

@@ -50,6 +50,7 @@ class Model(FusedModelBase):
 
     need_prior = True
     need_mom = True
+    lowp_ok = True
 
     def __init__(self, ND, prior_sig=1.0, bias="informative", momentum_decay=0.05):
         super().__init__()
@@ -62,6 +63,7 @@ class Model(FusedModelBase):
                 collect=None):
         N = self.ND * Ninflate
         lr_body, lr_head = (lrs[0], lrs[0]) if len(lrs) == 1 else (lrs[0], lrs[1])
+        self.refuse_lowp_grad_contract(sgd)
         st = self.state_for(net, net0)
         loss, out = self.forward_backward(st, net, x, y, criterion)
         nmode = self.draw_noise(st)

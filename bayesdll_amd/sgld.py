@@ -88,6 +88,7 @@ class Runner:
             self.model.graph = bool(args.graph)
         if getattr(args, "overlap", None) is not None:
             self.model.overlap = bool(args.overlap)
+        R.set_compute_dtype(self, args)
         self.optimizer = torch.optim.SGD(
             [{"params": [p for pn, p in self.net.named_parameters()
                          if self.net.readout_name not in pn], "lr": args.lr},
@@ -239,7 +240,7 @@ class Runner:
         """methods/sgld.py:367-385 — same file name and keys."""
         fname = os.path.join(self.args.log_dir, "ckpt.pt")
         self._export_sgd()
-        torch.save({"last_theta": self.net.state_dict(),
+        torch.save({"last_theta": R.net_state_dict(self),
                     "post_theta_mom1": self.post_theta_mom1,
                     "post_theta_mom2": self.post_theta_mom2 if self.nst > 0 else None,
                     "post_theta_cnt": self.post_theta_cnt,
@@ -287,6 +288,7 @@ class Model(FusedModelBase):
 
     need_prior = True
     need_mom = True  # SGD momentum buffer (used when momentum != 0)
+    lowp_ok = True
 
     def __init__(self, ND, prior_sig=1.0, bias="informative"):
         super().__init__()
@@ -298,6 +300,7 @@ class Model(FusedModelBase):
                 collect=None, clip_grad=None):
         N = self.ND * Ninflate
         lr_body, lr_head = (lrs[0], lrs[0]) if len(lrs) == 1 else (lrs[0], lrs[1])
+        self.refuse_lowp_grad_contract(sgd, clip_grad)
         st = self.state_for(net, net0)
         loss, out = self.forward_backward(st, net, x, y, criterion)
         nmode = self.draw_noise(st)

@@ -375,7 +375,9 @@ class _StackedSampler:
                  per_chain_batches=False, logger=None, graph=None, net0=None, per_chain=None,
                  health_every=0, ess_batch=0):
         from . import chains
-        from ._base import default_graph
+        from ._base import default_compute_dtype, default_graph, refuse_compute_dtype
+        refuse_compute_dtype(getattr(args, "compute_dtype", None) or default_compute_dtype(),
+                             "the stacked samplers (bayesdll_amd.stacked)")
         self._init_per_chain(per_chain, K_, args)
         if int(health_every) != health_every or int(health_every) < 0:
             raise ValueError(f"health_every must be an integer >= 0 (got {health_every!r})")
