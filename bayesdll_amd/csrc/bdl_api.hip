@@ -33,7 +33,7 @@
 // method, compiled in parallel), this file (host entry points of the C-ABI,
 // validation, launch geometry, the clip-norm / moments / sample kernels).
 #include <algorithm>
-#include "bdl_kernels.hpp"
+#include "bdl_chain_common.hpp"
 #include "bdl_measure.h"
 
 #include <mutex>
@@ -43,13 +43,6 @@ namespace bdl {
 namespace {
 
 thread_local std::string g_last_error;
-
-int fail(int code, const char* msg) {
-  g_last_error = msg;
-  return code;
-}
-
-int fail(int code, const std::string& msg) { return fail(code, msg.c_str()); }
 
 // Tunables (bdl_set_launch_config).  blocks_per_cu * #CUs workgroups, each
 // lane keeps `unroll` float4 groups in flight per iteration.  Defaults (2
@@ -73,8 +66,6 @@ int device_cu_count() {
   return cached[dev];
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // ---------------------------------------------------------------------------
 // Gradient-norm reduction for clip_grad_norm_ (csgld.py:250-251).  The SGLD
 // sampler gradient G = g + prior + noise is recomputed per element (Philox
@@ -87,12 +78,6 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
 // (deterministic) and writes (total_norm, coef).
 // ---------------------------------------------------------------------------
 constexpr int kMaxNormPartials = 2048;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 template <int NOISE, bool RECIP, bool PRIOR>
 __device__ __forceinline__ double sqnorm_fast(const KArgs& a, const StepConst& c, int64_t gb,
@@ -495,15 +480,14 @@ StepKernel pick_step(int method, int noise, int collect, int unroll) {
 
 int grid_for(int64_t ngroups, int per_block_groups) {
   const int64_t want = (ngroups + per_block_groups - 1) / per_block_groups;
-  const int64_t cap = (int64_t)device_cu_count() * g_blocks_per_cu;
-  return (int)std::max<int64_t>(1, std::min(want, cap));
+  return (int)capped_grid(want, (int64_t)device_cu_count() * g_blocks_per_cu);
 }
 
 int grid_sample(int64_t ngroups, int blocks_per_cu, int unroll) {
   const int64_t per_block = (int64_t)kBlock * unroll;
   const int64_t want = (ngroups + per_block - 1) / per_block;
-  const int64_t cap = (int64_t)device_cu_count() * (blocks_per_cu > 0 ? blocks_per_cu : BDL_SAMPLE_BPC);
-  return (int)std::max<int64_t>(1, std::min(want, cap));
+  return (int)capped_grid(
+      want, (int64_t)device_cu_count() * (blocks_per_cu > 0 ? blocks_per_cu : BDL_SAMPLE_BPC));
 }
 
 // Validate a step descriptor, pick the kernel instance and launch it; `clip`
@@ -542,9 +526,9 @@ int check_runs_and_grad(const bdl_step_args* s, const char* what) {
                 "2730 with grad_base; merge parameter groups)");
   if (!s->grad && !s->grad_base)
     return fail(BDL_ERR_NULL, std::string(what) + ": grad or grad_base is required");
-  if (s->grad && !aligned16(s->grad))
+  if (misaligned(s->grad, 15))
     return fail(BDL_ERR_ALIGN, std::string(what) + ": grad not 16-B aligned");
-  if (s->grad_base && (reinterpret_cast<uintptr_t>(s->grad_base) & 7u))
+  if (misaligned(s->grad_base, 7))
     return fail(BDL_ERR_ALIGN, std::string(what) + ": grad_base not 8-B aligned");
   if (s->chain_groups &&
       (s->chain_groups > 0xFFFFFFFFull ||
@@ -560,18 +544,12 @@ int check_runs_and_grad(const bdl_step_args* s, const char* what) {
 // step kernels launched into a capture (to recognise their nodes), and the
 // instantiated graph + node the thread's next bdl_sgmcmc_step rewrites
 // instead of launching.  While a redirect is set, every other launching entry
-// point refuses (no_redirect): their launches would go to the stream, mixed
-// with node rewrites.
+// point refuses (no_redirect, bdl_chain_common.hpp): their launches would go to
+// the stream, mixed with node rewrites.
 std::mutex g_captured_mu;
 std::vector<const void*> g_captured_funcs;  // step kernels launched into a capture
 thread_local hipGraphExec_t g_redirect_exec = nullptr;
 thread_local hipGraphNode_t g_redirect_node = nullptr;
-
-int no_redirect(const char* what) {
-  if (!g_redirect_exec) return BDL_OK;
-  return fail(BDL_ERR_ARG, std::string(what) + ": a graph redirect is active (bdl_graph_redirect); "
-              "only bdl_sgmcmc_step rewrites a node");
-}
 
 int launch_step(const bdl_step_args* s, const float* clip, hipStream_t stream, bool bare = false) {
   if (!s) return fail(BDL_ERR_NULL, "bdl_sgmcmc_step: null args");
@@ -601,7 +579,7 @@ int launch_step(const bdl_step_args* s, const float* clip, hipStream_t stream, b
     return fail(BDL_ERR_ARG, "bdl_sgmcmc_step: grad-only methods cannot collect");
   const void* ptrs[] = {s->theta, s->mom, s->prior_mean, s->noise, s->mom1, s->mom2};
   for (const void* p : ptrs)
-    if (p && !aligned16(p)) return fail(BDL_ERR_ALIGN, "bdl_sgmcmc_step: vector not 16-B aligned");
+    if (misaligned(p, 15)) return fail(BDL_ERR_ALIGN, "bdl_sgmcmc_step: vector not 16-B aligned");
 
   const int unroll = g_unroll;
   StepKernel k = bare ? (s->method == BDL_CSGHMC ? pick_step_csghmc_bare(s->collect, unroll)
@@ -613,7 +591,7 @@ int launch_step(const bdl_step_args* s, const float* clip, hipStream_t stream, b
   const int64_t per_iter = (int64_t)kBlock * unroll;
   const int64_t cap = (int64_t)device_cu_count() * g_blocks_per_cu;
   int64_t iters = (ngroups + per_iter - 1) / per_iter;
-  int64_t grid = std::max<int64_t>(1, std::min(iters, cap));
+  int64_t grid = capped_grid(iters, cap);
   int64_t iters_per_block = (iters + grid - 1) / grid;
   grid = (iters + iters_per_block - 1) / iters_per_block;
 
@@ -683,11 +661,7 @@ int launch_step(const bdl_step_args* s, const float* clip, hipStream_t stream, b
     return BDL_OK;
   }
   hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), run_lds_bytes(s), stream, a);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    g_last_error = std::string("bdl_sgmcmc_step: launch failed: ") + hipGetErrorString(err);
-    return BDL_ERR_LAUNCH;
-  }
+  if (const int rc = launched("bdl_sgmcmc_step")) return rc;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (stream && hipStreamIsCapturing(stream, &cs) == hipSuccess &&
       cs == hipStreamCaptureStatusActive) {
@@ -824,10 +798,9 @@ MixKernel pick_mix(int nr, int nw, int schedule, int unroll) {
 
 }  // namespace
 
-// errors of the other host translation units (bdl_arena.hip)
+// what bdl_chain_common.hpp's host helpers stand on, here and in the other
+// translation units
 void set_last_error(const std::string& msg) { g_last_error = msg; }
-
-// for the launching entry points of the other translation units (bdl_diag.hip)
 bool graph_redirect_active() { return g_redirect_exec != nullptr; }
 int cu_count() { return device_cu_count(); }
 
@@ -983,7 +956,7 @@ int bdl_sgld_step_clipped(const bdl_step_args* s, float max_norm, void* workspac
   if (const int rc = no_redirect("bdl_sgld_step_clipped")) return rc;
   if (!s) return fail(BDL_ERR_NULL, "bdl_sgld_step_clipped: null args");
   if (!workspace) return fail(BDL_ERR_NULL, "bdl_sgld_step_clipped: null workspace");
-  if (!aligned16(workspace)) return fail(BDL_ERR_ALIGN, "bdl_sgld_step_clipped: workspace not 16-B aligned");
+  if (misaligned(workspace, 15)) return fail(BDL_ERR_ALIGN, "bdl_sgld_step_clipped: workspace not 16-B aligned");
   if (s->method != BDL_SGLD)
     return fail(BDL_ERR_ARG, "bdl_sgld_step_clipped: only the SGLD sampler clips its gradient");
   if (s->flags & BDL_FLAG_GRAD_READY)
@@ -1026,7 +999,7 @@ int bdl_sgld_step_clipped(const bdl_step_args* s, float max_norm, void* workspac
   const int64_t ngroups = (s->n + 3) / 4;
   const int64_t iters = (ngroups + 2 * kBlock - 1) / (2 * kBlock);
   const int64_t cap = std::min<int64_t>((int64_t)device_cu_count() * g_blocks_per_cu, kMaxNormPartials);
-  const int grid = (int)std::max<int64_t>(1, std::min(iters, cap));
+  const int grid = (int)capped_grid(iters, cap);
   const size_t shmem = run_lds_bytes(s);
   switch (s->noise_mode) {
     case BDL_NOISE_NONE:
@@ -1040,11 +1013,7 @@ int bdl_sgld_step_clipped(const bdl_step_args* s, float max_norm, void* workspac
       break;
   }
   hipLaunchKernelGGL(bdl_clip_finalize_kernel, dim3(1), dim3(kBlock), 0, st, partials, grid, max_norm, ws);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    g_last_error = std::string("bdl_sgld_step_clipped: launch failed: ") + hipGetErrorString(err);
-    return BDL_ERR_LAUNCH;
-  }
+  if (const int rc = launched("bdl_sgld_step_clipped")) return rc;
   return launch_step(s, ws, st);
 }
 
@@ -1074,7 +1043,7 @@ int bdl_adam_step(const bdl_step_args* s, const bdl_adam_args* ad, void* stream)
   const void* ptrs[] = {s->theta, s->mom, s->prior_mean, s->noise, s->mom1, s->mom2,
                         ad->adam_m, ad->adam_v, ad->sgd_buf};
   for (const void* p : ptrs)
-    if (p && !aligned16(p)) return fail(BDL_ERR_ALIGN, "bdl_adam_step: vector not 16-B aligned");
+    if (misaligned(p, 15)) return fail(BDL_ERR_ALIGN, "bdl_adam_step: vector not 16-B aligned");
   const int unroll = grad_only ? 2 : g_unroll;
   StepKernel k = pick_adam(s->noise_mode, s->collect, grad_only, unroll);
   if (!k) return fail(BDL_ERR_ARG, "bdl_adam_step: unsupported noise/collect combination");
@@ -1130,14 +1099,9 @@ int bdl_adam_step(const bdl_step_args* s, const bdl_adam_args* ad, void* stream)
   const int64_t per_iter = (int64_t)kBlock * unroll;
   const int64_t iters = (ngroups + per_iter - 1) / per_iter;
   const int64_t cap = (int64_t)device_cu_count() * g_blocks_per_cu;
-  const int grid = (int)std::max<int64_t>(1, std::min(iters, cap));
+  const int grid = (int)capped_grid(iters, cap);
   hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), run_lds_bytes(s), (hipStream_t)stream, a);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    g_last_error = std::string("bdl_adam_step: launch failed: ") + hipGetErrorString(err);
-    return BDL_ERR_LAUNCH;
-  }
-  return BDL_OK;
+  return launched("bdl_adam_step");
 }
 
 int bdl_moments_update(const bdl_moments_args* m, void* stream) {
@@ -1149,19 +1113,14 @@ int bdl_moments_update(const bdl_moments_args* m, void* stream) {
   if (!m->theta || !m->mom1) return fail(BDL_ERR_NULL, "bdl_moments_update: theta/mom1 required");
   const void* ptrs[] = {m->theta, m->mom1, m->mom2};
   for (const void* p : ptrs)
-    if (p && !aligned16(p)) return fail(BDL_ERR_ALIGN, "bdl_moments_update: vector not 16-B aligned");
+    if (misaligned(p, 15)) return fail(BDL_ERR_ALIGN, "bdl_moments_update: vector not 16-B aligned");
   MArgs a{m->theta, m->mom1, m->mom2, m->n, m->collect, (m->flags & BDL_FLAG_RECIP_DIV) ? 1 : 0,
           m->collect_a, m->collect_b, recip_or(m->inv_collect_a, m->collect_a),
           recip_or(m->inv_collect_b, m->collect_b)};
   hipLaunchKernelGGL(pick_moments(m->collect, a.recip != 0, m->mom2 != nullptr),
                      dim3(grid_for((m->n + 3) / 4, kBlock * 4)), dim3(kBlock), 0,
                      (hipStream_t)stream, a);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    g_last_error = std::string("bdl_moments_update: launch failed: ") + hipGetErrorString(err);
-    return BDL_ERR_LAUNCH;
-  }
-  return BDL_OK;
+  return launched("bdl_moments_update");
 }
 
 int bdl_posterior_sample(const bdl_sample_args* s, void* stream) {
@@ -1175,7 +1134,7 @@ int bdl_posterior_sample(const bdl_sample_args* s, void* stream) {
     return fail(BDL_ERR_NULL, "bdl_posterior_sample: out, mom1 (and noise) required");
   const void* ptrs[] = {s->out, s->mom1, s->mom2, s->noise};
   for (const void* p : ptrs)
-    if (p && !aligned16(p)) return fail(BDL_ERR_ALIGN, "bdl_posterior_sample: vector not 16-B aligned");
+    if (misaligned(p, 15)) return fail(BDL_ERR_ALIGN, "bdl_posterior_sample: vector not 16-B aligned");
   if (s->chain_groups &&
       (s->chain_groups > 0xFFFFFFFFull || (uint64_t)((s->n + 3) / 4) > 0xFFFFFFFFull))
     return fail(BDL_ERR_ARG, "bdl_posterior_sample: stacked chains need every float4 group "
@@ -1196,12 +1155,7 @@ int bdl_posterior_sample(const bdl_sample_args* s, void* stream) {
                                  s->noise_mode, floored, su),
                      dim3(grid_sample((s->n + 3) / 4, s->blocks_per_cu, su)), dim3(kBlock), 0,
                      (hipStream_t)stream, a);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    g_last_error = std::string("bdl_posterior_sample: launch failed: ") + hipGetErrorString(err);
-    return BDL_ERR_LAUNCH;
-  }
-  return BDL_OK;
+  return launched("bdl_posterior_sample");
 }
 
 int bdl_stream_mix_schedule(const float* const* reads, int32_t nreads, float* const* writes,
@@ -1221,12 +1175,12 @@ int bdl_stream_mix_schedule(const float* const* reads, int32_t nreads, float* co
                 "(3,4) (5,4) (7,5)");
   MixArgs a{};
   for (int i = 0; i < nreads; ++i) {
-    if (!reads[i] || !aligned16(reads[i]))
+    if (!reads[i] || misaligned(reads[i], 15))
       return fail(BDL_ERR_ALIGN, "bdl_stream_mix: read stream null or not 16-B aligned");
     a.r[i] = reads[i];
   }
   for (int i = 0; i < nwrites; ++i) {
-    if (!writes[i] || !aligned16(writes[i]))
+    if (!writes[i] || misaligned(writes[i], 15))
       return fail(BDL_ERR_ALIGN, "bdl_stream_mix: write stream null or not 16-B aligned");
     a.w[i] = writes[i];
   }
@@ -1235,14 +1189,9 @@ int bdl_stream_mix_schedule(const float* const* reads, int32_t nreads, float* co
   const int u = unroll == 1 || unroll == 4 ? unroll : 2;
   const int64_t ngroups = (n + 3) / 4, per = (int64_t)kBlock * u;
   const int64_t want = (ngroups + per - 1) / per;
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)device_cu_count() * blocks_per_cu));
+  const int grid = (int)capped_grid(want, (int64_t)device_cu_count() * blocks_per_cu);
   hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, a);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    g_last_error = std::string("bdl_stream_mix: launch failed: ") + hipGetErrorString(err);
-    return BDL_ERR_LAUNCH;
-  }
-  return BDL_OK;
+  return launched("bdl_stream_mix");
 }
 
 int bdl_stream_mix(const float* const* reads, int32_t nreads, float* const* writes,
@@ -1258,16 +1207,11 @@ int bdl_philox_normal(float* out, int64_t n, uint64_t seed, uint64_t chain, uint
   if (n < 0) return fail(BDL_ERR_ARG, "bdl_philox_normal: n < 0");
   if (n == 0) return BDL_OK;
   if (!out) return fail(BDL_ERR_NULL, "bdl_philox_normal: null out");
-  if (!aligned16(out)) return fail(BDL_ERR_ALIGN, "bdl_philox_normal: out not 16-B aligned");
+  if (misaligned(out, 15)) return fail(BDL_ERR_ALIGN, "bdl_philox_normal: out not 16-B aligned");
   if (const int rc = check_philox_range("bdl_philox_normal", n, 0, chain, 0)) return rc;
   hipLaunchKernelGGL(bdl_philox_kernel, dim3(grid_for((n + 3) / 4, kBlock * 4)), dim3(kBlock), 0,
                      (hipStream_t)stream, out, n, seed, chain, step);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    g_last_error = std::string("bdl_philox_normal: launch failed: ") + hipGetErrorString(err);
-    return BDL_ERR_LAUNCH;
-  }
-  return BDL_OK;
+  return launched("bdl_philox_normal");
 }
 
 

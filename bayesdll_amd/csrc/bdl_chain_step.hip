@@ -20,7 +20,7 @@
 // step_noise4 under BDL_PHILOX_KEYS_PER_CALL).  Here that segment does not
 // hold the chain's values, so this unit is built WITHOUT that define and
 // instantiates only depths for which fresh_step_args is false (unroll_ok).
-#include "bdl_kernels.hpp"
+#include "bdl_chain_common.hpp"
 #include "bdl_chain_step.h"
 
 #ifdef BDL_PHILOX_KEYS_PER_CALL
@@ -28,20 +28,9 @@
 #endif
 
 namespace bdl {
-
-// bdl_api.hip
-void set_last_error(const std::string& msg);
-bool graph_redirect_active();
-int cu_count();
-
 namespace {
 
 constexpr int kChainWgPerCu = 2;  // default grid: this many workgroups per CU over all chains
-
-int fail(int code, const std::string& msg) {
-  set_last_error(msg);
-  return code;
-}
 
 // What the workgroups share: chain 0's pointers and the launch-uniform fields
 // in `base`; where chain k's differ.
@@ -156,8 +145,6 @@ ChainKernel pick_chain(int method, int noise, int collect, int unroll) {
   return nullptr;
 }
 
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 // the method / noise / collect table of the header
 const char* scope_error(int method, int noise, int collect) {
   if (method != BDL_CSGHMC && method != BDL_SGLD)
@@ -190,9 +177,7 @@ int bdl_chain_step_unroll_ok(int32_t method, int32_t noise_mode, int32_t collect
 
 int bdl_chain_step(const bdl_chain_step_args* d, void* stream) {
   const std::string W = "bdl_chain_step: ";
-  if (graph_redirect_active())
-    return fail(BDL_ERR_ARG, W + "a graph redirect is active (bdl_graph_redirect); "
-                "only bdl_sgmcmc_step rewrites a node");
+  if (const int rc = no_redirect("bdl_chain_step")) return rc;
   if (!d) return fail(BDL_ERR_NULL, W + "null args");
   if (d->chains < 1 || d->chains > BDL_CHAIN_STEP_MAX_CHAINS)
     return fail(BDL_ERR_ARG, W + "chains in [1, " + std::to_string(BDL_CHAIN_STEP_MAX_CHAINS) + "]");
@@ -227,12 +212,12 @@ int bdl_chain_step(const bdl_chain_step_args* d, void* stream) {
     return fail(BDL_ERR_NULL, W + "mom1 is required to collect");
   const void* vecs[] = {d->theta, d->grad, d->mom, d->prior_mean, d->noise, d->mom1, d->mom2};
   for (const void* p : vecs)
-    if (p && !aligned(p, 16)) return fail(BDL_ERR_ALIGN, W + "vector not 16-B aligned");
-  if (!aligned(d->scalars, 16)) return fail(BDL_ERR_ALIGN, W + "scalars not 16-B aligned");
-  if (!aligned(d->runs, 8)) return fail(BDL_ERR_ALIGN, W + "runs not 8-B aligned");
-  if (d->grad_base && !aligned(d->grad_base, 8))
+    if (misaligned(p, 15)) return fail(BDL_ERR_ALIGN, W + "vector not 16-B aligned");
+  if (misaligned(d->scalars, 15)) return fail(BDL_ERR_ALIGN, W + "scalars not 16-B aligned");
+  if (misaligned(d->runs, 7)) return fail(BDL_ERR_ALIGN, W + "runs not 8-B aligned");
+  if (misaligned(d->grad_base, 7))
     return fail(BDL_ERR_ALIGN, W + "grad_base not 8-B aligned");
-  if (d->nonfinite && !aligned(d->nonfinite, 4))
+  if (misaligned(d->nonfinite, 3))
     return fail(BDL_ERR_ALIGN, W + "nonfinite not 4-B aligned");
   if (d->nonfinite_per_chain != 0 && d->nonfinite_per_chain != 1)
     return fail(BDL_ERR_ARG, W + "nonfinite_per_chain is 0 or 1");
@@ -255,15 +240,11 @@ int bdl_chain_step(const bdl_chain_step_args* d, void* stream) {
     return fail(BDL_ERR_ARG, W + "no kernel instance at this unroll depth for this method / noise "
                 "/ collect (bdl_chain_step_unroll_ok)");
 
-  const int64_t ngroups = (d->n1 + 3) / 4;
-  const int64_t per_iter = (int64_t)kBlock * unroll;
-  const int64_t iters = (ngroups + per_iter - 1) / per_iter;
   int64_t bpc = d->blocks_per_chain;
-  if (bpc == 0) {
-    const int64_t want = ((int64_t)cu_count() * kChainWgPerCu + d->chains - 1) / d->chains;
-    bpc = std::max<int64_t>(
-        1, std::min<int64_t>(std::min(want, iters), BDL_CHAIN_STEP_MAX_BLOCKS_PER_CHAIN));
-  }
+  if (bpc == 0)
+    bpc = blocks_per_chain(kChainWgPerCu, d->chains,
+                           std::min<int64_t>(block_iters(d->n1, (int64_t)kBlock * unroll),
+                                             BDL_CHAIN_STEP_MAX_BLOCKS_PER_CHAIN));
 
   CArgs ca;
   memset(&ca, 0, sizeof(ca));
@@ -300,12 +281,7 @@ int bdl_chain_step(const bdl_chain_step_args* d, void* stream) {
   const size_t lds = (size_t)d->nruns * (sizeof(bdl_run) + (d->grad_base ? sizeof(int64_t) : 0));
   hipLaunchKernelGGL(kern, dim3((unsigned)bpc, (unsigned)d->chains), dim3(kBlock), lds,
                      (hipStream_t)stream, ca, d->scalars);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_last_error(W + "launch failed: " + hipGetErrorString(err));
-    return BDL_ERR_LAUNCH;
-  }
-  return BDL_OK;
+  return launched("bdl_chain_step");
 }
 
 }  // extern "C"

@@ -11,30 +11,20 @@
 // that a table of many small tensors does not pile up on workgroup 0; the (up
 // to 3) unaligned elements before and after the body go to three lanes each of
 // that first workgroup.  The norm is reduced like the clip norm of
-// bdl_api.hip: per-lane fp64 fma accumulators, a 64-lane butterfly, the 4 waves
-// through LDS, one partial per workgroup written with an ordinary store, then
+// bdl_api.hip: per-lane fp64 fma accumulators, a 64-lane butterfly
+// (bdl_chain_common.hpp's wave_sum), the 4 waves through LDS, one partial per
+// workgroup written with an ordinary store, then
 // one workgroup per chain that combines the chain's partials in a fixed order.
 // No atomics, no host synchronisation, no allocation.
-#include "bdl_kernels.hpp"
+#include "bdl_chain_common.hpp"
 #include "bdl_clip.h"
 
 namespace bdl {
-
-// bdl_api.hip
-void set_last_error(const std::string& msg);
-bool graph_redirect_active();
-int cu_count();
-
 namespace {
 
 constexpr int kClipUnroll = 4;                                 // float4 groups in flight per lane
 constexpr int64_t kClipIter = (int64_t)kBlock * kClipUnroll;   // groups per block iteration
 constexpr int kClipWgPerCu = 4;                                // default grid: this many per CU
-
-int fail(int code, const std::string& msg) {
-  set_last_error(msg);
-  return code;
-}
 
 // Chain k's slice of a segment: `head` elements up to the first 16-B
 // boundary, `nbody` float4 groups from `body` on, `tail` elements after them.
@@ -56,17 +46,6 @@ __device__ __forceinline__ Slice slice_of(const bdl_clip_segment& s, int k) {
   c.nbody = (s.numel - h) >> 2;
   c.tail = (int)(s.numel - h - 4 * c.nbody);
   return c;
-}
-
-// The workgroup of this chain that starts segment i (and owns its head / tail).
-__device__ __forceinline__ uint32_t rotated_block(int i) {
-  return (blockIdx.x + gridDim.x - (uint32_t)i % gridDim.x) % gridDim.x;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 // The block's sum in thread 0 (4 waves through LDS, in wave order).
@@ -211,15 +190,13 @@ int64_t bdl_chain_clip_workspace_bytes(int32_t chains) {
 }
 
 int bdl_chain_clip(const bdl_chain_clip_args* d, void* stream) {
-  if (graph_redirect_active())
-    return fail(BDL_ERR_ARG, "bdl_chain_clip: a graph redirect is active (bdl_graph_redirect); "
-                "only bdl_sgmcmc_step rewrites a node");
+  if (const int rc = no_redirect("bdl_chain_clip")) return rc;
   if (!d) return fail(BDL_ERR_NULL, "bdl_chain_clip: null args");
   if (!d->segments) return fail(BDL_ERR_NULL, "bdl_chain_clip: null segments");
   if (!d->workspace) return fail(BDL_ERR_NULL, "bdl_chain_clip: null workspace");
-  if (reinterpret_cast<uintptr_t>(d->workspace) & 15u)
+  if (misaligned(d->workspace, 15))
     return fail(BDL_ERR_ALIGN, "bdl_chain_clip: workspace not 16-B aligned");
-  if (reinterpret_cast<uintptr_t>(d->segments) & 7u)
+  if (misaligned(d->segments, 7))
     return fail(BDL_ERR_ALIGN, "bdl_chain_clip: segments not 8-B aligned");
   if (d->chains < 1 || d->chains > BDL_CLIP_MAX_CHAINS)
     return fail(BDL_ERR_ARG, "bdl_chain_clip: chains in [1, " +
@@ -233,10 +210,8 @@ int bdl_chain_clip(const bdl_chain_clip_args* d, void* stream) {
                 std::to_string(BDL_CLIP_MAX_BLOCKS_PER_CHAIN) + "]");
 
   int bpc = d->blocks_per_chain;
-  if (bpc == 0) {  // the table's sizes are on the device: fill the CUs, whatever it holds
-    const int64_t want = ((int64_t)cu_count() * kClipWgPerCu + d->chains - 1) / d->chains;
-    bpc = (int)std::max<int64_t>(1, std::min<int64_t>(want, BDL_CLIP_MAX_BLOCKS_PER_CHAIN));
-  }
+  if (bpc == 0)  // the table's sizes are on the device: fill the CUs, whatever it holds
+    bpc = (int)blocks_per_chain(kClipWgPerCu, d->chains, BDL_CLIP_MAX_BLOCKS_PER_CHAIN);
   float* out = reinterpret_cast<float*>(d->workspace);
   double* partials =
       reinterpret_cast<double*>(reinterpret_cast<char*>(d->workspace) + coef_bytes(d->chains));
@@ -248,12 +223,7 @@ int bdl_chain_clip(const bdl_chain_clip_args* d, void* stream) {
                      partials, bpc, d->max_norm, out);
   hipLaunchKernelGGL(bdl_chain_scale_kernel, grid, dim3(kBlock), 0, st, d->segments, d->nsegments,
                      out);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_last_error(std::string("bdl_chain_clip: launch failed: ") + hipGetErrorString(err));
-    return BDL_ERR_LAUNCH;
-  }
-  return BDL_OK;
+  return launched("bdl_chain_clip");
 }
 
 }  // extern "C"

@@ -9,55 +9,18 @@
 // elements and walks the chains, K read streams a chain slot apart (chain 0
 // peeled, the loop unrolled by 4 so eight loads are in flight per lane), then
 // finishes its four elements (four IEEE divisions and a square root per
-// element, none per chain).  Its summary is reduced like bdl_chain_diag's:
-// per-lane accumulators, a 64-lane butterfly, the block's 4 waves through LDS,
-// one partial per workgroup written with ordinary stores, and a one-workgroup
-// launch that combines the partials in a fixed order.  No atomics, no host
-// synchronisation, no allocation.
-#include "bdl_kernels.hpp"
+// element, none per chain).  Its summary is reduced by bdl_chain_common.hpp
+// (shared with bdl_diag.hip): per-lane accumulators, a 64-lane butterfly, the
+// block's 4 waves through LDS, one partial per workgroup written with ordinary
+// stores, and a one-workgroup launch that combines the partials in a fixed
+// order.  No atomics, no host synchronisation, no allocation.
+#include "bdl_chain_common.hpp"
 #include "bdl_ess.h"
 
 namespace bdl {
-
-// bdl_api.hip
-void set_last_error(const std::string& msg);
-bool graph_redirect_active();
-int cu_count();
-
 namespace {
 
-constexpr int64_t kPartialsOffset = 128;  // the summary, padded; then the partials
-constexpr int kEssBpc = 2;                // default workgroups per CU
-
-int fail(int code, const std::string& msg) {
-  set_last_error(msg);
-  return code;
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-// [a, a + bytes) and [b, b + bytes) share a byte (null: no vector)
-bool overlap(const void* a, const void* b, uint64_t abytes, uint64_t bbytes) {
-  if (!a || !b) return false;
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return x < y ? y - x < abytes : x - y < bbytes;
-}
-
-template <bool GUARD>
-__device__ __forceinline__ f4v eload(const float* __restrict__ p, int64_t e, int64_t n) {
-  if constexpr (GUARD)
-    return ld4(p, e, n);  // element-wise past the last full group; never past n
-  else
-    return vload(p + e);
-}
-
-template <bool GUARD>
-__device__ __forceinline__ void estore(float* __restrict__ p, int64_t e, int64_t n, f4v v) {
-  if constexpr (GUARD)
-    st4(p, e, n, v);
-  else
-    vstore(p + e, v);
-}
+constexpr int kEssBpc = 2;  // default workgroups per CU
 
 // ------------------------------------------------------------------ the fold
 struct FArgs {
@@ -81,14 +44,14 @@ __device__ __forceinline__ void fold_group(const FArgs& a, int64_t o, int64_t gi
   constexpr bool kFirstBatch = FLAGS & BDL_ESS_FIRST_BATCH;
   const int64_t e = gi * 4;
   const f4v z = {0.f, 0.f, 0.f, 0.f};
-  const f4v x = eload<GUARD>(a.theta + o, e, a.n);
+  const f4v x = gload<GUARD>(a.theta + o, e, a.n);
   f4v sm = z, M = z, bs = z, B = z;
   if constexpr (!kFirstSample) {
-    sm = eload<GUARD>(a.smean + o, e, a.n);
-    M = eload<GUARD>(a.sM2 + o, e, a.n);
+    sm = gload<GUARD>(a.smean + o, e, a.n);
+    M = gload<GUARD>(a.sM2 + o, e, a.n);
   }
-  if constexpr (!kFirstInBatch) bs = eload<GUARD>(a.bsum + o, e, a.n);
-  if constexpr (kClose && !kFirstBatch) B = eload<GUARD>(a.bM2 + o, e, a.n);
+  if constexpr (!kFirstInBatch) bs = gload<GUARD>(a.bsum + o, e, a.n);
+  if constexpr (kClose && !kFirstBatch) B = gload<GUARD>(a.bM2 + o, e, a.n);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if constexpr (kFirstSample) {
@@ -118,12 +81,12 @@ __device__ __forceinline__ void fold_group(const FArgs& a, int64_t o, int64_t gi
       }
     }
   }
-  estore<GUARD>(a.smean + o, e, a.n, sm);
-  estore<GUARD>(a.sM2 + o, e, a.n, M);
+  gstore<GUARD>(a.smean + o, e, a.n, sm);
+  gstore<GUARD>(a.sM2 + o, e, a.n, M);
   if constexpr (kClose)
-    estore<GUARD>(a.bM2 + o, e, a.n, B);
+    gstore<GUARD>(a.bM2 + o, e, a.n, B);
   else
-    estore<GUARD>(a.bsum + o, e, a.n, bs);
+    gstore<GUARD>(a.bsum + o, e, a.n, bs);
 }
 
 // Grid (blocks per chain, chains): a workgroup stays inside one chain.  An
@@ -177,83 +140,37 @@ struct EArgs {
   float thr0, thr1, thr2;
 };
 
-// A lane's / wave's / block's statistics.  Empty: mn = +Inf (every evaluated
-// ess is finite) and argmin = INT64_MAX, so `combine` needs no special case.
-struct Stat {
-  int64_t n_eval, n_deg, n_nonf, below0, below1, below2, argmin;
-  double sum;
-  float mn;
+using Stat = Extreme<false>;  // of ess: every evaluated one is finite
+
+// bdl_ess_summary <-> Stat
+struct EssSummary {
+  static constexpr bool kMax = false;
+  static __device__ __forceinline__ Stat load(const bdl_ess_summary& p) {
+    Stat s;
+    s.n_eval = p.n_eval;
+    s.n_deg = p.n_degenerate;
+    s.n_nonf = p.n_nonfinite;
+    s.hit0 = p.n_below[0];
+    s.hit1 = p.n_below[1];
+    s.hit2 = p.n_below[2];
+    s.arg = p.argmin;
+    s.sum = p.ess_sum;
+    s.ext = p.ess_min;
+    return s;
+  }
+  static __device__ __forceinline__ void store(bdl_ess_summary* __restrict__ out, const Stat& s) {
+    out->n_eval = s.n_eval;
+    out->n_degenerate = s.n_deg;
+    out->n_nonfinite = s.n_nonf;
+    out->argmin = s.arg;
+    out->n_below[0] = s.hit0;
+    out->n_below[1] = s.hit1;
+    out->n_below[2] = s.hit2;
+    out->ess_sum = s.sum;
+    out->ess_min = s.ext;
+    out->pad = 0.0f;
+  }
 };
-
-__device__ __forceinline__ Stat stat_empty() {
-  Stat s;
-  s.n_eval = s.n_deg = s.n_nonf = s.below0 = s.below1 = s.below2 = 0;
-  s.argmin = INT64_MAX;
-  s.sum = 0.0;
-  s.mn = __builtin_inff();
-  return s;
-}
-
-// the smaller minimum wins, the lower index among equals
-__device__ __forceinline__ Stat combine(Stat a, const Stat& b) {
-  a.n_eval += b.n_eval;
-  a.n_deg += b.n_deg;
-  a.n_nonf += b.n_nonf;
-  a.below0 += b.below0;
-  a.below1 += b.below1;
-  a.below2 += b.below2;
-  a.sum += b.sum;
-  if (b.mn < a.mn || (b.mn == a.mn && b.argmin < a.argmin)) {
-    a.mn = b.mn;
-    a.argmin = b.argmin;
-  }
-  return a;
-}
-
-__device__ __forceinline__ Stat wave_combine(Stat s) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    Stat o;
-    o.n_eval = __shfl_xor(s.n_eval, off, 64);
-    o.n_deg = __shfl_xor(s.n_deg, off, 64);
-    o.n_nonf = __shfl_xor(s.n_nonf, off, 64);
-    o.below0 = __shfl_xor(s.below0, off, 64);
-    o.below1 = __shfl_xor(s.below1, off, 64);
-    o.below2 = __shfl_xor(s.below2, off, 64);
-    o.argmin = __shfl_xor(s.argmin, off, 64);
-    o.sum = __shfl_xor(s.sum, off, 64);
-    o.mn = __shfl_xor(s.mn, off, 64);
-    // both partners must form the same value: the lower lane's first
-    s = (threadIdx.x & off) ? combine(o, s) : combine(s, o);
-  }
-  return s;
-}
-
-// The block's statistics in thread 0 (4 waves through LDS, in wave order).
-__device__ __forceinline__ Stat block_combine(Stat s) {
-  __shared__ Stat s_wave[kBlock / 64];
-  s = wave_combine(s);
-  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int w = 1; w < kBlock / 64; ++w) s = combine(s, s_wave[w]);
-  }
-  return s;
-}
-
-__device__ __forceinline__ void store_stat(bdl_ess_summary* __restrict__ out, const Stat& s) {
-  out->n_eval = s.n_eval;
-  out->n_degenerate = s.n_deg;
-  out->n_nonfinite = s.n_nonf;
-  out->argmin = s.argmin;
-  out->n_below[0] = s.below0;
-  out->n_below[1] = s.below1;
-  out->n_below[2] = s.below2;
-  out->ess_sum = s.sum;
-  out->ess_min = s.mn;
-  out->pad = 0.0f;
-}
 
 __device__ __forceinline__ void accum4(const f4v m, const f4v q, f4v& SW, f4v& SV) {
 #pragma unroll
@@ -277,19 +194,10 @@ __device__ __forceinline__ void finish_elem(const EArgs& a, float SW, float SV, 
     ++s.n_deg;
   } else {
     es = ess;
-    if (!__builtin_isfinite(ess)) {
+    if (!__builtin_isfinite(ess))
       ++s.n_nonf;
-    } else {
-      ++s.n_eval;
-      s.sum += (double)ess;
-      s.below0 += ess < a.thr0;
-      s.below1 += ess < a.thr1;
-      s.below2 += ess < a.thr2;
-      if (ess < s.mn) {  // a lane's elements ascend: strict keeps the lowest index
-        s.mn = ess;
-        s.argmin = idx;
-      }
-    }
+    else
+      count_value(s, ess, idx, a.thr0, a.thr1, a.thr2);
   }
 }
 
@@ -299,8 +207,8 @@ template <bool GUARD>
 __device__ __forceinline__ void ess_group(const EArgs& a, int64_t gi, Stat& s) {
   const int64_t e = gi * 4;
   const f4v z = {0.f, 0.f, 0.f, 0.f};
-  const f4v m0 = eload<GUARD>(a.sM2, e, a.n);
-  const f4v q0 = eload<GUARD>(a.bM2, e, a.n);
+  const f4v m0 = gload<GUARD>(a.sM2, e, a.n);
+  const f4v q0 = gload<GUARD>(a.bM2, e, a.n);
   f4v SW = z, SV = z;
   accum4(m0, q0, SW, SV);
   int k = 1;
@@ -309,16 +217,16 @@ __device__ __forceinline__ void ess_group(const EArgs& a, int64_t gi, Stat& s) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int64_t o = (int64_t)(k + u) * a.slot;
-      m[u] = eload<GUARD>(a.sM2 + o, e, a.n);
-      q[u] = eload<GUARD>(a.bM2 + o, e, a.n);
+      m[u] = gload<GUARD>(a.sM2 + o, e, a.n);
+      q[u] = gload<GUARD>(a.bM2 + o, e, a.n);
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) accum4(m[u], q[u], SW, SV);
   }
   for (; k < a.chains; ++k) {
     const int64_t o = (int64_t)k * a.slot;
-    const f4v m = eload<GUARD>(a.sM2 + o, e, a.n);
-    const f4v q = eload<GUARD>(a.bM2 + o, e, a.n);
+    const f4v m = gload<GUARD>(a.sM2 + o, e, a.n);
+    const f4v q = gload<GUARD>(a.bM2 + o, e, a.n);
     accum4(m, q, SW, SV);
   }
   f4v es = z, mc = z;
@@ -330,54 +238,29 @@ __device__ __forceinline__ void ess_group(const EArgs& a, int64_t gi, Stat& s) {
     es[j] = xe;
     mc[j] = xm;
   }
-  if (a.ess) estore<GUARD>(a.ess, e, a.n, es);
-  if (a.mcse) estore<GUARD>(a.mcse, e, a.n, mc);
+  if (a.ess) gstore<GUARD>(a.ess, e, a.n, es);
+  if (a.mcse) gstore<GUARD>(a.mcse, e, a.n, mc);
 }
 
-// Grid-stride sweep in bdl_chain_diag_kernel's shape.  gridDim.x <=
-// BDL_ESS_MAX_GRID (the host's cap): one partial per workgroup.
+// The fold's sweep (unguarded full iterations, one guarded tail iteration; the
+// loop is kept per kernel: as a shared function it re-allocates registers).
+// gridDim.x <= BDL_ESS_MAX_GRID (the host's cap): one partial per workgroup.
 __global__ __launch_bounds__(kBlock) void bdl_chain_ess_kernel(const EArgs a) {
   const int64_t ngroups = (a.n + 3) >> 2, nfull = a.n >> 2;
   const int64_t stride = (int64_t)gridDim.x * kBlock;
-  Stat s = stat_empty();
+  Stat s = Stat::empty();
   int64_t gb = (int64_t)blockIdx.x * kBlock;
   for (; gb + kBlock <= nfull; gb += stride) ess_group<false>(a, gb + threadIdx.x, s);
   if (gb < ngroups) {
     const int64_t gi = gb + threadIdx.x;
     if (gi < ngroups) ess_group<true>(a, gi, s);
   }
-  s = block_combine(s);
-  if (threadIdx.x == 0) store_stat(a.partials + blockIdx.x, s);
+  store_partial<EssSummary>(a.partials, s);
 }
 
-// One workgroup: the partials in a fixed order (thread t takes t, t + 256,
-// ...; then the wave butterfly and the waves in order), the empty case's
-// conventions, the summary.
 __global__ __launch_bounds__(kBlock) void bdl_chain_ess_finalize_kernel(
     const bdl_ess_summary* __restrict__ partials, int nparts, bdl_ess_summary* __restrict__ out) {
-  Stat s = stat_empty();
-  for (int i = threadIdx.x; i < nparts; i += kBlock) {
-    const bdl_ess_summary& p = partials[i];
-    Stat o;
-    o.n_eval = p.n_eval;
-    o.n_deg = p.n_degenerate;
-    o.n_nonf = p.n_nonfinite;
-    o.below0 = p.n_below[0];
-    o.below1 = p.n_below[1];
-    o.below2 = p.n_below[2];
-    o.argmin = p.argmin;
-    o.sum = p.ess_sum;
-    o.mn = p.ess_min;
-    s = combine(s, o);
-  }
-  s = block_combine(s);
-  if (threadIdx.x == 0) {
-    if (s.n_eval == 0) {
-      s.mn = 0.0f;
-      s.argmin = -1;
-    }
-    store_stat(out, s);
-  }
+  finalize_summary<EssSummary>(partials, nparts, out);
 }
 
 // what both entry points check of the stacked layout; nullptr: fine
@@ -385,11 +268,7 @@ const char* layout_error(int32_t chains, int64_t n, uint64_t chain_groups, int32
   if (chains < 1 || chains > BDL_ESS_MAX_CHAINS) return "chains must be in [1, 65535]";
   if (n < 1) return "n must be >= 1";
   if (grid_blocks < 0 || grid_blocks > BDL_ESS_MAX_GRID) return "grid_blocks in [0, 2048]";
-  // every element index 4*chain_groups*k + j must fit the signed 64-bit index
-  if (chain_groups > (uint64_t)(INT64_MAX / 4) / (uint64_t)chains)
-    return "chains * chain_groups overflows the element index";
-  if ((uint64_t)n > 4 * chain_groups) return "n exceeds the chain slot (4 * chain_groups)";
-  return nullptr;
+  return stacked_slot_error(chains, n, chain_groups);
 }
 
 }  // namespace
@@ -401,9 +280,7 @@ extern "C" {
 
 int bdl_chain_ess_fold(const bdl_ess_fold_args* d, void* stream) {
   const std::string me = "bdl_chain_ess_fold: ";
-  if (graph_redirect_active())
-    return fail(BDL_ERR_ARG, me + "a graph redirect is active (bdl_graph_redirect); "
-                "only bdl_sgmcmc_step rewrites a node");
+  if (const int rc = no_redirect("bdl_chain_ess_fold")) return rc;
   if (!d) return fail(BDL_ERR_NULL, me + "null args");
   if (!d->theta) return fail(BDL_ERR_NULL, me + "null theta");
   if (!d->smean || !d->sM2 || !d->bM2)
@@ -432,7 +309,7 @@ int bdl_chain_ess_fold(const bdl_ess_fold_args* d, void* stream) {
   float* const bsum = b > 1 ? d->bsum : nullptr;  // never touched at batch == 1
   const void* ptrs[] = {d->theta, bsum, d->smean, d->sM2, d->bM2};
   for (const void* q : ptrs)
-    if (q && !aligned16(q)) return fail(BDL_ERR_ALIGN, me + "vector not 16-B aligned");
+    if (misaligned(q, 15)) return fail(BDL_ERR_ALIGN, me + "vector not 16-B aligned");
   const uint64_t bytes = 4 * (4 * d->chain_groups * (uint64_t)(d->chains - 1) + (uint64_t)d->n);
   for (int i = 0; i < 5; ++i)
     for (int j = i + 1; j < 5; ++j)
@@ -452,19 +329,12 @@ int bdl_chain_ess_fold(const bdl_ess_fold_args* d, void* stream) {
   a.fs = d->fs;
   a.fb = d->fb;
   a.c = d->c;
-  const int64_t ngroups = (d->n + 3) / 4;
-  const int64_t need = (ngroups + kBlock - 1) / kBlock;
   const int64_t cap = d->grid_blocks > 0
                           ? d->grid_blocks
                           : std::max<int64_t>(1, (int64_t)cu_count() * kEssBpc / d->chains);
-  const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(need, cap), BDL_ESS_MAX_GRID));
+  const int gx = (int)capped_grid(block_iters(d->n, kBlock), std::min<int64_t>(cap, BDL_ESS_MAX_GRID));
   hipLaunchKernelGGL(k, dim3(gx, d->chains), dim3(kBlock), 0, (hipStream_t)stream, a);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_last_error(me + "launch failed: " + hipGetErrorString(err));
-    return BDL_ERR_LAUNCH;
-  }
-  return BDL_OK;
+  return launched("bdl_chain_ess_fold");
 }
 
 int64_t bdl_chain_ess_workspace_bytes(int64_t n) {
@@ -474,9 +344,7 @@ int64_t bdl_chain_ess_workspace_bytes(int64_t n) {
 
 int bdl_chain_ess(const bdl_chain_ess_args* d, void* stream) {
   const std::string me = "bdl_chain_ess: ";
-  if (graph_redirect_active())
-    return fail(BDL_ERR_ARG, me + "a graph redirect is active (bdl_graph_redirect); "
-                "only bdl_sgmcmc_step rewrites a node");
+  if (const int rc = no_redirect("bdl_chain_ess")) return rc;
   if (!d) return fail(BDL_ERR_NULL, me + "null args");
   if (!d->sM2 || !d->bM2) return fail(BDL_ERR_NULL, me + "sM2 and bM2 are required");
   if (!d->workspace) return fail(BDL_ERR_NULL, me + "null workspace");
@@ -491,8 +359,8 @@ int bdl_chain_ess(const bdl_chain_ess_args* d, void* stream) {
   if (d->batches > d->samples) return fail(BDL_ERR_ARG, me + "batches exceeds samples");
   const void* ptrs[] = {d->sM2, d->bM2, d->ess, d->mcse};
   for (const void* q : ptrs)
-    if (q && !aligned16(q)) return fail(BDL_ERR_ALIGN, me + "vector not 16-B aligned");
-  if (!aligned16(d->workspace)) return fail(BDL_ERR_ALIGN, me + "workspace not 16-B aligned");
+    if (misaligned(q, 15)) return fail(BDL_ERR_ALIGN, me + "vector not 16-B aligned");
+  if (misaligned(d->workspace, 15)) return fail(BDL_ERR_ALIGN, me + "workspace not 16-B aligned");
   const uint64_t in = 4 * (4 * d->chain_groups * (uint64_t)(d->chains - 1) + (uint64_t)d->n);
   const uint64_t out = 4 * (uint64_t)d->n;
   const uint64_t wsb = (uint64_t)bdl_chain_ess_workspace_bytes(d->n);
@@ -506,8 +374,7 @@ int bdl_chain_ess(const bdl_chain_ess_args* d, void* stream) {
     return fail(BDL_ERR_ARG, me + "the workspace overlaps an input");
 
   bdl_ess_summary* summary = reinterpret_cast<bdl_ess_summary*>(d->workspace);
-  bdl_ess_summary* partials = reinterpret_cast<bdl_ess_summary*>(
-      reinterpret_cast<char*>(d->workspace) + kPartialsOffset);
+  bdl_ess_summary* partials = partials_of<bdl_ess_summary>(d->workspace);
   EArgs a;
   a.sM2 = d->sM2;
   a.bM2 = d->bM2;
@@ -524,22 +391,15 @@ int bdl_chain_ess(const bdl_chain_ess_args* d, void* stream) {
   a.thr1 = d->thresholds[1];
   a.thr2 = d->thresholds[2];
 
-  const int64_t ngroups = (d->n + 3) / 4;
-  const int64_t need = (ngroups + kBlock - 1) / kBlock;
   const int64_t cap = d->grid_blocks > 0
                           ? d->grid_blocks
                           : std::min<int64_t>((int64_t)cu_count() * kEssBpc, BDL_ESS_MAX_GRID);
-  const int grid = (int)std::max<int64_t>(1, std::min(need, cap));
+  const int grid = (int)capped_grid(block_iters(d->n, kBlock), cap);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(bdl_chain_ess_kernel, dim3(grid), dim3(kBlock), 0, st, a);
   hipLaunchKernelGGL(bdl_chain_ess_finalize_kernel, dim3(1), dim3(kBlock), 0, st, partials, grid,
                      summary);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_last_error(me + "launch failed: " + hipGetErrorString(err));
-    return BDL_ERR_LAUNCH;
-  }
-  return BDL_OK;
+  return launched("bdl_chain_ess");
 }
 
 }  // extern "C"

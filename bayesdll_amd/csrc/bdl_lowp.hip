@@ -9,28 +9,13 @@
 // chunk_multi), every load of an iteration before its arithmetic.  Philox
 // inputs are read from the kernel's own KArgs (this unit is built without
 // BDL_PHILOX_KEYS_PER_CALL).
-#include "bdl_kernels.hpp"
+#include "bdl_chain_common.hpp"
 #include "bdl_lowp.h"
 
 namespace bdl {
-
-// bdl_api.hip
-void set_last_error(const std::string& msg);
-bool graph_redirect_active();
-int cu_count();
-
 namespace {
 
 constexpr int kLowpBpc = 2;  // default workgroups per CU
-
-int fail(int code, const std::string& msg) {
-  set_last_error(msg);
-  return code;
-}
-
-bool misaligned(const void* p, uintptr_t mask) {
-  return (reinterpret_cast<uintptr_t>(p) & mask) != 0;
-}
 
 typedef unsigned short bf16_t;
 typedef bf16_t us4v __attribute__((ext_vector_type(4)));
@@ -53,22 +38,6 @@ __device__ __forceinline__ us4v bf16_rne4(f4v x) {
   o.z = bf16_rne(x.z);
   o.w = bf16_rne(x.w);
   return o;
-}
-
-template <bool GUARD>
-__device__ __forceinline__ f4v eload(const float* __restrict__ p, int64_t e, int64_t n) {
-  if constexpr (GUARD)
-    return ld4(p, e, n);  // element-wise past the last full group; never past n
-  else
-    return vload(p + e);
-}
-
-template <bool GUARD>
-__device__ __forceinline__ void estore(float* __restrict__ p, int64_t e, int64_t n, f4v v) {
-  if constexpr (GUARD)
-    st4(p, e, n, v);
-  else
-    vstore(p + e, v);
 }
 
 // How a lane handles one float4 group of an iteration.
@@ -114,7 +83,7 @@ __device__ __forceinline__ void lowp_iter(const KArgs& a, const StepConst& c,
     const bool vec = whole && run_end(rr) >= e + 4 && !(at & kNoFastPath) &&
                      !(reinterpret_cast<uintptr_t>(gp) & 7u);
     kind[u] = vec ? kVec : kElem;
-    th[u] = eload<GUARD>(a.theta, e, n);
+    th[u] = gload<GUARD>(a.theta, e, n);
     if (vec) {
       const us4v h = __builtin_nontemporal_load((const gus4v*)(gp + 2 * e));
       g[u].x = bf16_up(h.x);
@@ -136,12 +105,12 @@ __device__ __forceinline__ void lowp_iter(const KArgs& a, const StepConst& c,
           g[u][j] = bf16_up(*(const gbf16*)(lowp_grad(a, r) + 2 * (e + j)));
       }
     }
-    if (T::kMom || (METHOD == BDL_SGLD && c.sgd_mom_read)) v[u] = eload<GUARD>(a.mom, e, n);
-    if (T::kReadPrior) t0[u] = eload<GUARD>(a.prior_mean, e, n);
-    if (NOISE == BDL_NOISE_BUFFER) ep[u] = eload<GUARD>(a.noise, e, n);
+    if (T::kMom || (METHOD == BDL_SGLD && c.sgd_mom_read)) v[u] = gload<GUARD>(a.mom, e, n);
+    if (T::kReadPrior) t0[u] = gload<GUARD>(a.prior_mean, e, n);
+    if (NOISE == BDL_NOISE_BUFFER) ep[u] = gload<GUARD>(a.noise, e, n);
     if (T::kReadMoments) {
-      m1[u] = eload<GUARD>(a.mom1, e, n);
-      if (c.has_m2) m2[u] = eload<GUARD>(a.mom2, e, n);
+      m1[u] = gload<GUARD>(a.mom1, e, n);
+      if (c.has_m2) m2[u] = gload<GUARD>(a.mom2, e, n);
     }
   }
 #pragma unroll
@@ -165,7 +134,7 @@ __device__ __forceinline__ void lowp_iter(const KArgs& a, const StepConst& c,
       m2[u][j] = x2;
     }
     bad |= nonfinite4(th[u]);  // elements past n hold 0: never flagged
-    estore<GUARD>(a.theta, e, n, th[u]);
+    gstore<GUARD>(a.theta, e, n, th[u]);
     if (kind[u] == kVec) {
       // non-temporal like the fp32 streams: the next forward reads the shadow,
       // but at ViT-L/32 size it is 613 MB, past the 256 MiB Infinity Cache.
@@ -181,10 +150,10 @@ __device__ __forceinline__ void lowp_iter(const KArgs& a, const StepConst& c,
       for (int j = 0; j < 4; ++j)
         if (!(skip[u] & (1u << j))) *(gbf16*)(shadow + e + j) = bf16_rne(th[u][j]);
     }
-    if (T::kMom || (METHOD == BDL_SGLD && c.sgd_mom)) estore<GUARD>(a.mom, e, n, v[u]);
+    if (T::kMom || (METHOD == BDL_SGLD && c.sgd_mom)) gstore<GUARD>(a.mom, e, n, v[u]);
     if (T::kCollect) {
-      estore<GUARD>(a.mom1, e, n, m1[u]);
-      if (c.has_m2) estore<GUARD>(a.mom2, e, n, m2[u]);
+      gstore<GUARD>(a.mom1, e, n, m1[u]);
+      if (c.has_m2) gstore<GUARD>(a.mom2, e, n, m2[u]);
     }
   }
 }
@@ -316,9 +285,7 @@ extern "C" {
 
 int bdl_lowp_step(const bdl_lowp_args* s, void* stream) {
   const std::string me = "bdl_lowp_step: ";
-  if (graph_redirect_active())
-    return fail(BDL_ERR_ARG, me + "a graph redirect is active (bdl_graph_redirect); "
-                "only bdl_sgmcmc_step rewrites a node");
+  if (const int rc = no_redirect("bdl_lowp_step")) return rc;
   if (!s) return fail(BDL_ERR_NULL, me + "null args");
   if (s->n <= 0) return fail(BDL_ERR_ARG, me + "n must be >= 1");
   if (s->method != BDL_CSGHMC && s->method != BDL_SGHMC && s->method != BDL_SGLD)
@@ -376,11 +343,10 @@ int bdl_lowp_step(const bdl_lowp_args* s, void* stream) {
   LowpKernel k = pick_lowp(s->method, s->noise_mode, s->collect, s->unroll);
   if (!k) return fail(BDL_ERR_ARG, me + "no kernel for this method/noise/collect combination");
 
-  const int64_t per_iter = (int64_t)kBlock * s->unroll;
-  const int64_t iters = ((int64_t)groups + per_iter - 1) / per_iter;
   const int64_t grid =
       s->blocks > 0 ? s->blocks
-                    : std::max<int64_t>(1, std::min(iters, (int64_t)cu_count() * kLowpBpc));
+                    : capped_grid(block_iters(s->n, (int64_t)kBlock * s->unroll),
+                                  (int64_t)cu_count() * kLowpBpc);
 
   KArgs a{};
   a.theta = s->theta;
@@ -421,19 +387,14 @@ int bdl_lowp_step(const bdl_lowp_args* s, void* stream) {
 
   hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), lds, (hipStream_t)stream, a,
                      s->shadow);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess)
-    return fail(BDL_ERR_LAUNCH, me + "launch failed: " + hipGetErrorString(err));
-  return BDL_OK;
+  return launched("bdl_lowp_step");
 }
 
 int bdl_lowp_shadow(const float* theta, uint16_t* shadow, const bdl_run* runs, int32_t nruns,
                     int64_t n, void* stream) {
   const std::string me = "bdl_lowp_shadow: ";
   (void)runs;  // every element is written, whatever its run's attributes
-  if (graph_redirect_active())
-    return fail(BDL_ERR_ARG, me + "a graph redirect is active (bdl_graph_redirect); "
-                "only bdl_sgmcmc_step rewrites a node");
+  if (const int rc = no_redirect("bdl_lowp_shadow")) return rc;
   if (!theta) return fail(BDL_ERR_NULL, me + "null theta");
   if (!shadow) return fail(BDL_ERR_NULL, me + "null shadow");
   if (n <= 0) return fail(BDL_ERR_ARG, me + "n must be >= 1");
@@ -441,13 +402,10 @@ int bdl_lowp_shadow(const float* theta, uint16_t* shadow, const bdl_run* runs, i
   if (misaligned(theta, 15)) return fail(BDL_ERR_ALIGN, me + "theta not 16-B aligned");
   if (misaligned(shadow, 7)) return fail(BDL_ERR_ALIGN, me + "shadow not 8-B aligned");
   const int64_t want = ((n >> 2) + kBlock - 1) / kBlock;
-  const int64_t grid = std::max<int64_t>(1, std::min(want, (int64_t)cu_count() * 4));
+  const int64_t grid = capped_grid(want, (int64_t)cu_count() * 4);
   hipLaunchKernelGGL(bdl_lowp_shadow_kernel, dim3((unsigned)grid), dim3(kBlock), 0,
                      (hipStream_t)stream, theta, shadow, n);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess)
-    return fail(BDL_ERR_LAUNCH, me + "launch failed: " + hipGetErrorString(err));
-  return BDL_OK;
+  return launched("bdl_lowp_shadow");
 }
 
 }  // extern "C"

@@ -22,27 +22,16 @@
 // pair measured 2.6-3.5 % faster this way at the stacked mlp_mnist sizes and
 // the same at 1 GiB (tools/chain_stats_timing.py).
 // BDL_STATS_NT_LOADS builds the non-temporal form for that comparison.
-#include "bdl_kernels.hpp"
+#include "bdl_chain_common.hpp"
 #include "bdl_stats.h"
 
 namespace bdl {
-
-// bdl_api.hip
-void set_last_error(const std::string& msg);
-bool graph_redirect_active();
-int cu_count();
-
 namespace {
 
 constexpr int kStatsUnroll = 4;                                  // units in flight per lane and stream
 constexpr int64_t kStatsIter = (int64_t)kBlock * kStatsUnroll;   // units per block iteration
 constexpr int kStatsWgPerCu = 4;                                 // default grid: this many per CU
 constexpr int kSums = 5;                                         // G2, V2, D2, DG, VG
-
-int fail(int code, const std::string& msg) {
-  set_last_error(msg);
-  return code;
-}
 
 struct StatsK {
   const float* theta;
@@ -59,16 +48,6 @@ __device__ __forceinline__ f4v ldv(const float* p) {
 #else
   return *reinterpret_cast<const f4v*>(p);
 #endif
-}
-
-__device__ __forceinline__ uint32_t rotated_block(int i) {
-  return (blockIdx.x + gridDim.x - (uint32_t)i % gridDim.x) % gridDim.x;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 // One element's five products, exact in double, accumulated with fp64 fma.
@@ -241,8 +220,6 @@ void launch_sweep(dim3 grid, hipStream_t st, const StatsK& k, double* partials) 
   hipLaunchKernelGGL((bdl_chain_stats_kernel<MOM, PRIOR>), grid, dim3(kBlock), 0, st, k, partials);
 }
 
-bool misaligned(const void* p, uintptr_t mask) { return reinterpret_cast<uintptr_t>(p) & mask; }
-
 }  // namespace
 }  // namespace bdl
 
@@ -258,9 +235,7 @@ int64_t bdl_chain_stats_workspace_bytes(int32_t chains, int32_t nsegments) {
 }
 
 int bdl_chain_stats(const bdl_chain_stats_args* d, void* stream) {
-  if (graph_redirect_active())
-    return fail(BDL_ERR_ARG, "bdl_chain_stats: a graph redirect is active (bdl_graph_redirect); "
-                "only bdl_sgmcmc_step rewrites a node");
+  if (const int rc = no_redirect("bdl_chain_stats")) return rc;
   if (!d) return fail(BDL_ERR_NULL, "bdl_chain_stats: null args");
   if (!d->theta) return fail(BDL_ERR_NULL, "bdl_chain_stats: null theta");
   if (!d->segments) return fail(BDL_ERR_NULL, "bdl_chain_stats: null segments");
@@ -301,10 +276,8 @@ int bdl_chain_stats(const bdl_chain_stats_args* d, void* stream) {
     return fail(BDL_ERR_ARG, "bdl_chain_stats: accumulate must be 0 or 1");
 
   int bpc = d->blocks_per_chain;
-  if (bpc == 0) {  // the table's sizes are on the device: fill the CUs, whatever it holds
-    const int64_t want = ((int64_t)cu_count() * kStatsWgPerCu + d->chains - 1) / d->chains;
-    bpc = (int)std::max<int64_t>(1, std::min<int64_t>(want, BDL_STATS_MAX_BLOCKS_PER_CHAIN));
-  }
+  if (bpc == 0)  // the table's sizes are on the device: fill the CUs, whatever it holds
+    bpc = (int)blocks_per_chain(kStatsWgPerCu, d->chains, BDL_STATS_MAX_BLOCKS_PER_CHAIN);
   StatsK k;
   k.theta = d->theta;
   k.mom = d->mom;
@@ -323,12 +296,7 @@ int bdl_chain_stats(const bdl_chain_stats_args* d, void* stream) {
   hipLaunchKernelGGL(bdl_chain_stats_combine_kernel, dim3((unsigned)((total + kBlock - 1) / kBlock)),
                      dim3(kBlock), 0, st, partials, bpc, d->nsegments, d->chains, d->segments,
                      d->lr_table, d->lr_row_stride, d->lr[0], d->lr[1], d->accumulate, d->acc);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_last_error(std::string("bdl_chain_stats: launch failed: ") + hipGetErrorString(err));
-    return BDL_ERR_LAUNCH;
-  }
-  return BDL_OK;
+  return launched("bdl_chain_stats");
 }
 
 }  // extern "C"

@@ -441,17 +441,60 @@ def posterior_sample(out, mom1, mom2, *, var_mode, ratio=1.0, var_floor=1e-12, n
 
 
 DIAG_OUTPUTS = ("pooled_mean", "pooled_var", "rhat")
-_DIAG_WS = {}  # device index -> workspace (summary + per-workgroup partials)
+_SCRATCH = {}  # (kind, device index, ...) -> a cached device workspace
 
 
-class DiagResult(dict):
-    """chain_diag's result: the requested output tensors by name and
+def _scratch(key, make):
+    """The cached device workspace under `key`, made on first use."""
+    ws = _SCRATCH.get(key)
+    if ws is None:
+        ws = _SCRATCH[key] = make()
+    return ws
+
+
+def _byte_scratch(kind, dev, nbytes):
+    return _scratch((kind, dev.index),
+                    lambda: torch.empty(int(nbytes()), dtype=torch.uint8, device=dev))
+
+
+def _stacked_layout(what, vectors, chains, chain_groups, n, chains_error=None,
+                    device_error="all vectors must be on one device"):
+    """The checks every stacked diagnostic makes of its layout and vectors
+    ((name, tensor) pairs): chains in range (chains_error(chains): the unit's
+    own bound and text, else 1 .. ESS_MAX_CHAINS), 1 <= n <= 4 * chain_groups,
+    each vector a contiguous HIP tensor that holds every chain's n elements,
+    all on one device.  Returns (chains, chain_groups, n, device)."""
+    chains, chain_groups, n = int(chains), int(chain_groups), int(n)
+    if chains_error is not None:
+        why = chains_error(chains)
+        if why:
+            raise ValueError(f"{what}: {why}")
+    elif not 1 <= chains <= L.ESS_MAX_CHAINS:
+        raise ValueError(f"{what}: 1 <= chains <= {L.ESS_MAX_CHAINS} is required")
+    if not 1 <= n <= 4 * chain_groups:
+        raise ValueError(f"{what}: 1 <= n <= 4 * chain_groups is required")
+    need = 4 * chain_groups * (chains - 1) + n
+    dev = None
+    for nm, t in vectors:
+        L.require_hip(t, nm)
+        if not t.is_contiguous() or t.numel() < need:
+            raise ValueError(f"{what}: {nm} must be contiguous with at least {need} elements")
+        if dev is not None and t.device != dev:
+            raise ValueError(f"{what}: {device_error}")
+        dev = t.device
+    return chains, chain_groups, n, dev
+
+
+class _LazySummary(dict):
+    """A stacked diagnostic's result: the requested output tensors by name and
     `summary`, read lazily — the first access copies the struct from the
-    device (one D2H copy, one sync of the launch stream) and is cached."""
+    device (one D2H copy, one sync of the launch stream) and is cached.
+    decode(raw bytes, thresholds) -> the summary dict."""
 
-    def __init__(self, outs, ws, event, thresholds):
+    def __init__(self, outs, ws, event, thresholds, decode):
         super().__init__(outs)
         self._ws, self._event, self._thresholds, self._summary = ws, event, thresholds, None
+        self._decode = decode
 
     def __missing__(self, key):
         if key != "summary":
@@ -462,19 +505,29 @@ class DiagResult(dict):
     def summary(self):
         if self._summary is None:
             self._event.synchronize()
-            raw = self._ws.cpu().numpy().tobytes()
-            s = L.DiagSummary.from_buffer_copy(raw)
-            ne = int(s.n_eval)
-            above = [int(v) for v in s.n_above]
-            self._summary = {
-                "n_eval": ne, "n_degenerate": int(s.n_degenerate),
-                "n_nonfinite": int(s.n_nonfinite), "argmax": int(s.argmax), "n_above": above,
-                "rhat_sum": float(s.rhat_sum), "rhat_max": float(s.rhat_max),
-                "rhat_mean": float(s.rhat_sum) / ne if ne else float("nan"),
-                "share_above": [v / ne if ne else float("nan") for v in above],
-                "thresholds": list(self._thresholds)}
+            self._summary = self._decode(self._ws.cpu().numpy().tobytes(), self._thresholds)
             self._ws = None
         return self._summary
+
+
+def _diag_summary(raw, thresholds):
+    s = L.DiagSummary.from_buffer_copy(raw)
+    ne = int(s.n_eval)
+    above = [int(v) for v in s.n_above]
+    return {"n_eval": ne, "n_degenerate": int(s.n_degenerate),
+            "n_nonfinite": int(s.n_nonfinite), "argmax": int(s.argmax), "n_above": above,
+            "rhat_sum": float(s.rhat_sum), "rhat_max": float(s.rhat_max),
+            "rhat_mean": float(s.rhat_sum) / ne if ne else float("nan"),
+            "share_above": [v / ne if ne else float("nan") for v in above],
+            "thresholds": list(thresholds)}
+
+
+class DiagResult(_LazySummary):
+    """chain_diag's result (summary: bdl_diag_summary plus rhat_mean,
+    share_above and `thresholds`)."""
+
+    def __init__(self, outs, ws, event, thresholds):
+        super().__init__(outs, ws, event, thresholds, _diag_summary)
 
 
 def chain_diag(mom1, mom2, *, chains, chain_groups, n, var_mode, ratio, count, var_floor=1e-12,
@@ -495,25 +548,14 @@ def chain_diag(mom1, mom2, *, chains, chain_groups, n, var_mode, ratio, count, v
     L.require_hip(mom2, "mom2")
     if int(count) < 2:
         raise ValueError(f"chain_diag: R-hat needs at least 2 samples per chain (count = {count})")
-    chains, chain_groups, n = int(chains), int(chain_groups), int(n)
-    if chains < 2:
-        raise ValueError(f"chain_diag: at least 2 chains are required (chains = {chains})")
-    if not 1 <= n <= 4 * chain_groups:
-        raise ValueError("chain_diag: 1 <= n <= 4 * chain_groups is required")
-    need = 4 * chain_groups * (chains - 1) + n
-    for nm, t in (("mom1", mom1), ("mom2", mom2)):
-        if not t.is_contiguous() or t.numel() < need:
-            raise ValueError(f"chain_diag: {nm} must be contiguous with at least {need} elements")
-    if mom2.device != mom1.device:
-        raise ValueError("chain_diag: mom1 and mom2 must be on one device")
+    chains, chain_groups, n, dev = _stacked_layout(
+        "chain_diag", (("mom1", mom1), ("mom2", mom2)), chains, chain_groups, n,
+        chains_error=lambda k: f"at least 2 chains are required (chains = {k})" if k < 2 else None,
+        device_error="mom1 and mom2 must be on one device")
     want = tuple(want)
     if len(thresholds) != 3 or any(w not in DIAG_OUTPUTS for w in want):
         raise ValueError(f"chain_diag: three thresholds, and want from {DIAG_OUTPUTS}")
-    dev = mom1.device
-    ws = _DIAG_WS.get(dev.index)
-    if ws is None:
-        nbytes = int(L.lib().bdl_chain_diag_workspace_bytes(n))
-        ws = _DIAG_WS[dev.index] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _byte_scratch("diag", dev, lambda: L.lib().bdl_chain_diag_workspace_bytes(n))
     outs = {w: torch.empty(n, dtype=torch.float32, device=dev) for w in want}
     a = L.DiagArgs()
     a.mom1, a.mom2 = mom1.data_ptr(), mom2.data_ptr()
@@ -541,7 +583,6 @@ def chain_diag(mom1, mom2, *, chains, chain_groups, n, var_mode, ratio, count, v
 
 ESS_OUTPUTS = ("ess", "mcse")
 ESS_VECTORS = ("bsum", "smean", "sM2", "bM2")
-_ESS_WS = {}  # device index -> workspace (summary + per-workgroup partials)
 
 
 def ess_fold_bytes_per_elem(flags):
@@ -553,24 +594,6 @@ def ess_fold_bytes_per_elem(flags):
 def ess_bytes_per_elem(chains, outputs):
     """Algorithmic HBM bytes per evaluated element of one chain_ess sweep."""
     return E.report_bytes_per_elem(chains, outputs)
-
-
-def _ess_layout(what, vectors, chains, chain_groups, n):
-    chains, chain_groups, n = int(chains), int(chain_groups), int(n)
-    if not 1 <= chains <= L.ESS_MAX_CHAINS:
-        raise ValueError(f"{what}: 1 <= chains <= {L.ESS_MAX_CHAINS} is required")
-    if not 1 <= n <= 4 * chain_groups:
-        raise ValueError(f"{what}: 1 <= n <= 4 * chain_groups is required")
-    need = 4 * chain_groups * (chains - 1) + n
-    dev = None
-    for nm, t in vectors:
-        L.require_hip(t, nm)
-        if not t.is_contiguous() or t.numel() < need:
-            raise ValueError(f"{what}: {nm} must be contiguous with at least {need} elements")
-        if dev is not None and t.device != dev:
-            raise ValueError(f"{what}: all vectors must be on one device")
-        dev = t.device
-    return chains, chain_groups, n, dev
 
 
 def ess_fold(theta, bsum, smean, sM2, bM2, *, chains, chain_groups, n, sample, batch,
@@ -589,7 +612,7 @@ def ess_fold(theta, bsum, smean, sM2, bM2, *, chains, chain_groups, n, sample, b
         if bsum is None:
             raise ValueError("ess_fold: bsum is required with batch > 1")
         vecs.append(("bsum", bsum))
-    chains, chain_groups, n, dev = _ess_layout("ess_fold", vecs, chains, chain_groups, n)
+    chains, chain_groups, n, dev = _stacked_layout("ess_fold", vecs, chains, chain_groups, n)
     a = L.EssFoldArgs()
     a.theta, a.smean, a.sM2, a.bM2 = (t.data_ptr() for t in (theta, smean, sM2, bM2))
     a.bsum = bsum.data_ptr() if int(batch) > 1 else None
@@ -603,41 +626,24 @@ def ess_fold(theta, bsum, smean, sM2, bM2, *, chains, chain_groups, n, sample, b
 
 def chain_ess_workspace(device):
     """The report's device scratch (summary + per-workgroup partials), one per device."""
-    dev = torch.device(device)
-    ws = _ESS_WS.get(dev.index)
-    if ws is None:
-        nbytes = int(L.lib().bdl_chain_ess_workspace_bytes(1))
-        ws = _ESS_WS[dev.index] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    return ws
+    return _byte_scratch("ess", torch.device(device),
+                         lambda: L.lib().bdl_chain_ess_workspace_bytes(1))
 
 
-class EssResult(dict):
-    """chain_ess's result: the requested output tensors by name and `summary`
-    (the raw fields of bdl_ess_summary plus `thresholds`), read lazily — the
-    first access copies the struct from the device (one D2H copy, one sync of
-    the launch stream) and is cached."""
+def _ess_summary(raw, thresholds):
+    s = L.EssSummary.from_buffer_copy(raw)
+    return {"n_eval": int(s.n_eval), "n_degenerate": int(s.n_degenerate),
+            "n_nonfinite": int(s.n_nonfinite), "argmin": int(s.argmin),
+            "n_below": [int(v) for v in s.n_below], "ess_sum": float(s.ess_sum),
+            "ess_min": float(s.ess_min), "thresholds": list(thresholds)}
+
+
+class EssResult(_LazySummary):
+    """chain_ess's result (summary: the raw fields of bdl_ess_summary plus
+    `thresholds`)."""
 
     def __init__(self, outs, ws, event, thresholds):
-        super().__init__(outs)
-        self._ws, self._event, self._thresholds, self._summary = ws, event, thresholds, None
-
-    def __missing__(self, key):
-        if key != "summary":
-            raise KeyError(key)
-        return self.summary
-
-    @property
-    def summary(self):
-        if self._summary is None:
-            self._event.synchronize()
-            s = L.EssSummary.from_buffer_copy(self._ws.cpu().numpy().tobytes())
-            self._summary = {
-                "n_eval": int(s.n_eval), "n_degenerate": int(s.n_degenerate),
-                "n_nonfinite": int(s.n_nonfinite), "argmin": int(s.argmin),
-                "n_below": [int(v) for v in s.n_below], "ess_sum": float(s.ess_sum),
-                "ess_min": float(s.ess_min), "thresholds": list(self._thresholds)}
-            self._ws = None
-        return self._summary
+        super().__init__(outs, ws, event, thresholds, _ess_summary)
 
 
 def chain_ess(sM2, bM2, *, chains, chain_groups, n, samples, batches,
@@ -658,7 +664,7 @@ def chain_ess(sM2, bM2, *, chains, chain_groups, n, samples, batches,
     thresholds = E.thresholds(thresholds)
     if any(w not in ESS_OUTPUTS for w in want):
         raise ValueError(f"chain_ess: want from {ESS_OUTPUTS}")
-    chains, chain_groups, n, dev = _ess_layout("chain_ess", (("sM2", sM2), ("bM2", bM2)), chains,
+    chains, chain_groups, n, dev = _stacked_layout("chain_ess", (("sM2", sM2), ("bM2", bM2)), chains,
                                                chain_groups, n)
     ws = chain_ess_workspace(dev)
     outs = {w: torch.empty(n, dtype=torch.float32, device=dev) for w in want}
@@ -677,9 +683,6 @@ def chain_ess(sM2, bM2, *, chains, chain_groups, n, samples, batches,
     ev = torch.cuda.Event()
     ev.record(torch.cuda.current_stream(dev))
     return EssResult(outs, snap, ev, thresholds)
-
-
-_CLIP_WS = {}  # (device index, chains) -> workspace ((norm, coef) per chain + partials)
 
 
 def clip_bytes_per_elem(clipped_share=1.0):
@@ -726,9 +729,8 @@ def chain_clip(segments, nsegments, chains, max_norm, workspace=None, blocks_per
         raise ValueError(f"chain_clip: max_norm must be > 0 (got {max_norm})")
     chains, dev = int(chains), segments.device
     if workspace is None:
-        workspace = _CLIP_WS.get((dev.index, chains))
-        if workspace is None:
-            workspace = _CLIP_WS[(dev.index, chains)] = chain_clip_workspace(chains, dev)
+        workspace = _scratch(("clip", dev.index, chains),
+                             lambda: chain_clip_workspace(chains, dev))
     else:
         L.require_hip(workspace, "workspace")
         if workspace.device != dev or not workspace.is_contiguous() or \

@@ -55,6 +55,26 @@ from .cyclical import CyclicalSGMCMC
 from .flat import MAX_TENSOR_RUNS, build_runs, segment_attrs
 
 
+def _upload_table(device, *parts):
+    """Rows -> one pinned int64 host table (the parts, flattened, end to end)
+    -> one non-blocking upload.  Returns the flat device tensor."""
+    flat = [np.asarray(p, dtype=np.int64).reshape(-1) for p in parts]
+    host = torch.empty(sum(f.size for f in flat), dtype=torch.int64).pin_memory()
+    np.concatenate(flat, out=host.numpy())
+    return host.to(device, non_blocking=True)
+
+
+def _cached_table(cache, key, build, keep=8):
+    """cache[key], built on a miss; the oldest of `keep` entries makes room."""
+    tab = cache.get(key)
+    if tab is None:
+        tab = build()
+        if len(cache) >= keep:
+            cache.pop(next(iter(cache)))
+        cache[key] = tab
+    return tab
+
+
 class StackedState:
     """K chains' flat cSGHMC state of one network, stacked chain-major.
 
@@ -201,12 +221,8 @@ class StackedState:
                 raise ValueError("StackedState: gradients must be contiguous fp32 [K, *shape]")
             ptrs.append(g.data_ptr())
         key = self._gbound = tuple(ptrs)
-        tab = self._tables.get(key)
-        if tab is None:
-            tab = self._build_chain_table(ptrs) if self.chain_tables else self._build_table(ptrs)
-            if len(self._tables) >= 8:
-                self._tables.pop(next(iter(self._tables)))
-            self._tables[key] = tab
+        build = self._build_chain_table if self.chain_tables else self._build_table
+        tab = _cached_table(self._tables, key, lambda: build(ptrs))
         if self.chain_tables:
             self.chain_runs, self.chain_nruns, self.chain_gbase = tab
         else:
@@ -228,11 +244,7 @@ class StackedState:
                     at |= L.ATTR_GUNALIGNED
             rows.append((o + n, at))
         nt = len(rows)
-        host = torch.empty(2 * nt + self.K * nt, dtype=torch.int64).pin_memory()
-        h = host.numpy()
-        h[:2 * nt] = np.asarray(rows, dtype=np.int64).reshape(-1)
-        h[2 * nt:] = bases.reshape(-1)
-        dev = host.to(self.device, non_blocking=True)
+        dev = _upload_table(self.device, rows, bases)
         return dev[:2 * nt].view(nt, 2), nt, dev[2 * nt:].view(self.K, nt)
 
     def _build_table(self, ptrs):
@@ -253,11 +265,7 @@ class StackedState:
                 rows.append(((k + 1) * self.stride, L.ATTR_SKIP))
                 bases.append(0)
         nt = len(rows)
-        host = torch.empty(3 * nt, dtype=torch.int64).pin_memory()
-        h = host.numpy()
-        h[:2 * nt] = np.asarray(rows, dtype=np.int64).reshape(-1)
-        h[2 * nt:] = np.asarray(bases, dtype=np.int64)
-        dev = host.to(self.device, non_blocking=True)
+        dev = _upload_table(self.device, rows, bases)
         return dev[:2 * nt].view(nt, 2), nt, dev[2 * nt:]
 
     def grad_segments(self):
@@ -271,8 +279,8 @@ class StackedState:
         key = self._gbound
         if key is None:
             raise ValueError("StackedState: grad_segments before use_grads")
-        tab = self._seg_tables.get(key)
-        if tab is None:
+
+        def build():
             if self.grad_mode == "flat":
                 rows = [(self.grad.data_ptr() + 4 * o, n, self.stride)
                         for o, n, have in zip(self.offsets, self.numels, key) if have]
@@ -280,13 +288,9 @@ class StackedState:
                 rows = [(ptr, n, n) for n, ptr in zip(self.numels, key) if ptr]
             if not rows:
                 raise ValueError("StackedState: no tensor has a gradient to clip")
-            host = torch.empty(len(rows), 3, dtype=torch.int64).pin_memory()
-            host.numpy()[:] = np.asarray(rows, dtype=np.int64)
-            tab = (host.to(self.device, non_blocking=True), len(rows))
-            if len(self._seg_tables) >= 8:
-                self._seg_tables.pop(next(iter(self._seg_tables)))
-            self._seg_tables[key] = tab
-        return tab
+            return _upload_table(self.device, rows).view(len(rows), 3), len(rows)
+
+        return _cached_table(self._seg_tables, key, build)
 
     def stat_segments(self):
         """(device table, nsegments, tensor indices) of kernels.chain_stats for
@@ -299,8 +303,8 @@ class StackedState:
         key = self._gbound
         if key is None:
             raise ValueError("StackedState: stat_segments before use_grads")
-        tab = self._stat_tables.get(key)
-        if tab is None:
+
+        def build():
             flat = self.grad_mode == "flat"
             idx = [i for i, have in enumerate(key) if have]
             if not idx:
@@ -308,13 +312,9 @@ class StackedState:
             rows = [(self.grad.data_ptr() + 4 * self.offsets[i] if flat else key[i],
                      self.numels[i], self.stride if flat else self.numels[i], self.offsets[i],
                      1 if self.attrs[i] & L.ATTR_HEAD else 0) for i in idx]
-            host = torch.empty(len(rows), 5, dtype=torch.int64).pin_memory()
-            host.numpy()[:] = np.asarray(rows, dtype=np.int64)
-            tab = (host.to(self.device, non_blocking=True), len(rows), tuple(idx))
-            if len(self._stat_tables) >= 8:
-                self._stat_tables.pop(next(iter(self._stat_tables)))
-            self._stat_tables[key] = tab
-        return tab
+            return _upload_table(self.device, rows).view(len(rows), 5), len(rows), tuple(idx)
+
+        return _cached_table(self._stat_tables, key, build)
 
     def diverged(self, reset=True):
         bad = bool(self.nonfinite.any().item())
@@ -834,9 +834,27 @@ class _StackedSampler:
         self.draws += 1
 
     # ---------------------------------------------------------- diagnostics
+    def _component_keys(self):
+        """The collected posterior components' keys, in draw order."""
+        raise NotImplementedError
+
+    def _components(self, buf):
+        """Every collected component in turn: nst posterior draws into `buf`
+        from its `_moment_spec` (the method's variance form and ratio), or,
+        with nst = 0, its mean; yields the component's key per draw."""
+        for c in self._component_keys():
+            m1, m2, var_mode, ratio, _ = self._moment_spec(c)
+            for _ in range(max(1, self.nst)):
+                if self.nst == 0:
+                    buf.copy_(m1)
+                else:
+                    self._sample(buf, m1, m2, var_mode, ratio)
+                yield c
+
     def _latest_component(self):
         """The component collected last (None while nothing is collected)."""
-        raise NotImplementedError
+        keys = self._component_keys()
+        return keys[-1] if keys else None
 
     def _moment_spec(self, component):
         """(m1, m2, var_mode, ratio, count) of a collected component: the K
@@ -1141,21 +1159,8 @@ class StackedCSGHMC(_StackedSampler):
             self._accumulate(acc, loss, out, y)
         return self._epoch_result(acc)
 
-    def _components(self, buf):
-        """Every collected cycle: nst posterior draws (its Welford mean and
-        variance M2/(n-1), 1e-12 for a single sample; methods/csghmc.py:446-468)
-        or, with nst = 0, its mean."""
-        for c in sorted(self.mom1):
-            m1, m2, var_mode, ratio, _ = self._moment_spec(c)
-            for _ in range(max(1, self.nst)):
-                if self.nst == 0:
-                    buf.copy_(m1)
-                else:
-                    self._sample(buf, m1, m2, var_mode, ratio)
-                yield c
-
-    def _latest_component(self):
-        return max(self.mom1) if self.mom1 else None
+    def _component_keys(self):
+        return sorted(self.mom1)  # every collected cycle
 
     def _moment_spec(self, c):
         """Cycle c: Welford mean and M2 / (n - 1) with n the stored count —
@@ -1308,21 +1313,8 @@ class StackedSGLD(_StackedSampler):
             self._accumulate(acc, loss, out, y)
         return self._epoch_result(acc)
 
-    def _components(self, buf):
-        """nst posterior draws, var = cnt/(cnt-1) * (m2 - m1^2) (1.0 for one
-        sample; methods/sgld.py:324-350), or the posterior mean (nst = 0)."""
-        if self.m1 is None:
-            return
-        m1, m2, var_mode, ratio, _ = self._moment_spec(0)
-        for _ in range(max(1, self.nst)):
-            if self.nst == 0:
-                buf.copy_(m1)
-            else:
-                self._sample(buf, m1, m2, var_mode, ratio)
-            yield 0
-
-    def _latest_component(self):
-        return None if self.m1 is None else 0
+    def _component_keys(self):
+        return [] if self.m1 is None else [0]  # the one running component
 
     def _moment_spec(self, component=0):
         """The one component: running (m1, m2) over cnt collects, the burn-in
@@ -1412,20 +1404,8 @@ class StackedCSGLD(StackedSGLD):
         """Hook at every last_in_cycle step, after the step and its collect
         (bayesdll_amd.csgld.Runner._cycle_end)."""
 
-    def _components(self, buf):
-        """Every collected cycle: nst draws with var = spc/(spc-1) * (m2 - m1^2)
-        (ratio 1 for a one-sample cycle; methods/csgld.py:394-400), or its mean."""
-        for c in sorted(self.mom1):
-            m1, m2, var_mode, ratio, _ = self._moment_spec(c)
-            for _ in range(max(1, self.nst)):
-                if self.nst == 0:
-                    buf.copy_(m1)
-                else:
-                    self._sample(buf, m1, m2, var_mode, ratio)
-                yield c
-
-    def _latest_component(self):
-        return max(self.mom1) if self.mom1 else None
+    def _component_keys(self):
+        return sorted(self.mom1)  # every collected cycle
 
     def _moment_spec(self, c):
         """Cycle c: running (m1, m2) over its spc collects; var = spc/(spc-1) *
