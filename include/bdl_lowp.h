@@ -29,6 +29,9 @@
  *     such an element is never read: the padding of a stacked slot keeps
  *     whatever it holds in both.
  *   Results never depend on `blocks` or `unroll`.
+ *   Known limit: *nonfinite looks at the fp32 theta only (it is the fp32
+ *     step's flag), so a finite theta above the largest finite bf16 gives an
+ *     infinite shadow element without raising it.
  *
  * Sweep: grid-stride, 256-lane workgroups, the run table (and the gradient
  * bases) staged in LDS.  A lane takes `unroll` float4 groups per iteration,

@@ -5,12 +5,19 @@ stream, across launch geometries, flat gradient against the per-run base
 table, split launches, stacked keying with sentinels in the padding, SKIP
 elements, the shadow rounding and the divergence flag.
 
-One table serves all of it: test_gpu_noise_units.py's 39,426 elements
-(n % 4 = 2; runs whose offsets are not multiples of 4, so float4 groups span
-two runs; a head run; uninformative biases; a frozen tensor in the middle).
-In base-table mode every tensor's gradient is a bf16 tensor of its own, the
-first one placed one bf16 element off 8-B alignment.  With blocks = 2 every
-workgroup runs 5 to 20 iterations."""
+One table serves this file: test_gpu_noise_units.py's 39,426 elements
+(n % 4 = 2; one run boundary that is no multiple of 4, at 16,295, so one
+float4 group spans two runs; a head run; uninformative biases; a frozen tensor
+in the middle).  In base-table mode every tensor's gradient is a bf16 tensor
+of its own, the first one placed one bf16 element off 8-B alignment (that
+tensor alone is read element by element).  With blocks = 2 every workgroup
+runs 5 to 20 iterations; with the default grid every workgroup runs one.
+
+What this file does NOT reach — most instances at their own depth, launches
+without mom2, an iteration that holds a boundary group, a SKIP run and an
+unaligned base together — tests/test_gpu_lowp_instances.py covers on a table
+built for it, and tests/test_lowp_host.py proves on the CPU (lowp_ref.classify)
+which groups of which iterations take which path on both tables."""
 from types import SimpleNamespace
 
 import numpy as np

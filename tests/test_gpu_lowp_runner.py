@@ -1,6 +1,7 @@
 """bf16 compute through the sampler Models: an MLP (13 inputs, two hidden
-Linear layers of width 32, 5 classes, batch 8) stepped by the cSGHMC and SGLD
-Models with compute_dtype = bf16 against a hand-written loop — a bf16 copy of
+Linear layers of width 32, 5 classes, batch 8) stepped by the cSGHMC, SGLD,
+SGHMC and unclipped cSGLD samplers with compute_dtype = bf16 against a
+hand-written loop — a bf16 copy of
 the network forward and backward, its gradients upcast, the existing fp32
 kernels.sgmcmc_step on a plain fp32 state with Philox noise, theta.to(bf16)
 written back — bit for bit in theta, momentum and moments, the shadow equal to
@@ -276,6 +277,41 @@ def test_runner_in_bf16_equals_the_hand_loop_and_evaluates_in_fp32(method, tmp_p
     assert torch.as_tensor(logits_l).dtype == torch.float32
     assert torch.equal(torch.as_tensor(logits_l), torch.as_tensor(logits_h))
     assert el[0] == eh[0] and el[1] == eh[1]
+
+
+@pytest.mark.parametrize("method,geo,steps", [("sghmc", dict(epochs=2), 8),
+                                              ("csgld", dict(epochs=4, num_cycles=2), 16)],
+                         ids=["sghmc", "csgld-two-cycles"])
+def test_sghmc_and_unclipped_csgld_runners_in_bf16_equal_the_hand_loop(method, geo, steps,
+                                                                       tmp_path):
+    """SGHMC (8 steps) and cSGLD without clip_grad over two cycles of 8 steps
+    (the cycle boundary lies inside the run: the second cycle collects into
+    moments of its own) against the hand loop: fp32 kernels on the upcast
+    gradients plus theta.to(bf16)."""
+    train, test = _loader(5, 4), _loader(6, 2)
+    low = _runner(method, tmp_path / "low", "bf16", **geo)
+    seen = []
+    _watch_shadow(low, seen)
+    hand = _as_hand_loop(_runner(method, tmp_path / "hand", None, **geo))
+    low.train(train, None, test)
+    hand.train(train, None, test)
+    torch.cuda.synchronize()
+    sl, sh = low.model.flat, hand.model.flat
+    assert low.model.step_count == hand.model.step_count == steps
+    assert sl.shadow is not None and sh.shadow is None
+    assert torch.equal(sl.theta, sh.theta) and torch.equal(sl.mom, sh.mom)
+    assert torch.equal(sl.shadow, sl.theta.to(torch.bfloat16))
+    ml, mh = _moments(low), _moments(hand)
+    assert len(ml) == len(mh) >= (4 if method == "csgld" else 2)
+    for a, b in zip(ml, mh):
+        assert torch.equal(a, b)
+    if method == "csgld":  # both cycles collected, into different moments
+        assert sorted(low.cycle_theta_mom1) == sorted(hand.cycle_theta_mom1)
+        assert len(low.cycle_theta_mom1) == 2 and not torch.equal(ml[0], ml[2])
+    assert len(seen) == steps and all(seen)
+    for p, o in zip(low.net.parameters(), sl.offsets):
+        assert p.dtype == torch.bfloat16 and p.data_ptr() == sl.shadow.data_ptr() + 2 * o
+    assert not sl.diverged()
 
 
 def test_checkpoint_roundtrip_and_exact_resume_in_bf16(tmp_path):

@@ -3,10 +3,22 @@ a GPU: the header's declarations, the export table, the C struct layout against
 the ctypes mirror, every validation path of bdl_lowp_step / bdl_lowp_shadow
 (fake pointers: each call returns before any HIP call), the reference rounding
 against torch's on the CPU, and the refusals of FlatState, the samplers and the
-CLI."""
+CLI.
+
+And what the bf16 step's GPU tests rely on, proven on the CPU (the second half
+of this file): lowp_ref.classify restates the sweep of bdl_lowp.hip (full or
+guarded iteration, kVec / kElem / kNone per float4 group and the reason of
+every kElem) and is itself checked on hand-written tables with literal
+answers; table D (lowp_ref.TableD) at the instance tests' grid, and tables B
+and C at the stacked tests' geometry, reach the conditions those tests claim,
+at every depth, for the flat gradient and for the per-tensor base table.
+These are conditions, not measurements: a change of table, grid or sweep that
+loses one fails here.  Also: the library holds exactly the kernel instances
+the instance tests launch (by name)."""
 import ctypes as C
 import os
 import re
+import shutil
 import subprocess
 from types import SimpleNamespace
 
@@ -16,6 +28,9 @@ import torch
 import torch.nn as nn
 
 import lowp_ref as LR
+import stacked_tables as ST
+import step_ref as SR
+from test_gpu_noise_units import SEGMENTS
 from test_stacked_host import Net, host_only  # noqa: F401  (fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -332,3 +347,190 @@ def test_cli_parses_compute_dtype_and_refuses_it_with_stacked_chains(capsys):
     with pytest.raises(SystemExit):
         run.check_compute_dtype(ap, args)
     assert "stacked samplers have no bf16 step" in capsys.readouterr().err
+
+
+# ===================================================== the sweep, classified
+D = LR.TableD
+DEPTHS = [1, 2, 4]
+MODES = {"flat": None, "bases": D.PHASES}
+VEC, ELEM, NONE = LR.K_VEC, LR.K_ELEM, LR.K_NONE
+PRIOR, SKIP = SR.ATTR_PRIOR, SR.ATTR_SKIP
+
+
+# ------------------------------------------------------------- the classifier
+def test_classifier_on_hand_written_tables():
+    # 1. one tensor of 2 x 1024 + 6 elements, depth 1, one workgroup: two full
+    #    iterations of vector groups, then the guarded one: one whole group,
+    #    the tail group (2 elements), 254 lanes past the end
+    it = LR.classify([0], [2054], [PRIOR], None, 2054, 1, 1)
+    assert [(i.wg, i.index, i.gb, i.full) for i in it] == [(0, 0, 0, True), (0, 1, 256, True),
+                                                           (0, 2, 512, False)]
+    assert all((i.kind == VEC).all() for i in it[:2])
+    assert it[2].kind.tolist() == [VEC, ELEM] + [NONE] * 254
+    assert it[2].reason.tolist() == [0, LR.R_TAIL] + [0] * 254
+    # 2. two workgroups at depth 2 over 4096 + 2048 elements: grid-stride order
+    it = LR.classify([0], [6144], [PRIOR], None, 6144, 2, 2)
+    assert [(i.wg, i.index, i.gb, i.full) for i in it] == [(0, 0, 0, True), (0, 1, 1024, True),
+                                                           (1, 0, 512, True)]
+    # 3. 16 elements in 4 groups: a boundary at 6 (inside group 1), a SKIP
+    #    tensor [8, 12), then a tensor whose base is 2 B off; per-tensor runs
+    args = ([0, 6, 8, 12], [6, 2, 4, 4], [PRIOR, 0, PRIOR | SKIP, PRIOR])
+    k = LR.classify(*args, [0, 0, 0, 2], 16, 1, 1)[0]
+    assert not k.full  # 4 groups are no whole iteration
+    assert k.kind.tolist()[:5] == [VEC, ELEM, ELEM, ELEM, NONE]
+    assert k.reason.tolist()[:4] == [0, LR.R_BOUNDARY, LR.R_SKIP, LR.R_BASE]
+    #    the flat gradient: the last tensor is a vector group
+    k = LR.classify(*args, None, 16, 1, 1)[0]
+    assert k.kind.tolist()[:4] == [VEC, ELEM, ELEM, VEC]
+    # 4. flat runs merge equal neighbours (no boundary at 6), per-tensor runs do not
+    args = ([0, 6], [6, 1018], [PRIOR, PRIOR])
+    assert LR.classify(*args, None, 1024, 1, 1)[0].kind.tolist() == [VEC] * 256
+    k = LR.classify(*args, [0, 0], 1024, 1, 1)[0]
+    assert k.full and k.kind.tolist() == [VEC, ELEM] + [VEC] * 254
+    # 5. a gap between tensors and the rest up to n are SKIP runs (a stacked slot's padding)
+    k = LR.classify([0, 8], [6, 4], [PRIOR, PRIOR], None, 16, 1, 1)[0]
+    assert k.kind.tolist()[:4] == [VEC, ELEM, VEC, ELEM]
+    assert k.reason.tolist()[:4] == [0, LR.R_BOUNDARY, 0, LR.R_SKIP]
+
+
+def test_run_table_equals_bdl_build_runs_and_attrs_equal_segment_attrs():
+    from bayesdll_amd.flat import build_runs, segment_attrs
+    assert D.attrs == segment_attrs(D.names, "head", "uninformative",
+                                    [nm not in D.FROZEN for nm in D.names])
+    for lay in (ST.table_a(), ST.table_b(), ST.table_c()):
+        segs = lay.stacked_segments()
+        o, k, a = ([s[i] for s in segs] for i in range(3))
+        ends, attrs = LR.run_table(o, k, a, lay.n)
+        assert np.column_stack([ends, attrs]).tolist() == lay.flat_runs().tolist()
+    ends, attrs = LR.run_table(D.offsets, D.numels, D.attrs, D.n)
+    assert np.column_stack([ends, attrs]).tolist() == \
+        build_runs(D.offsets, D.numels, D.attrs, D.n).tolist()
+    ends, _ = LR.run_table(D.offsets, D.numels, D.attrs, D.n, per_tensor=True)
+    assert ends.tolist() == [o + k for o, k in zip(D.offsets, D.numels)]
+
+
+def test_table_d_layout():
+    assert (D.n, D.n % 4, len(D.SEGMENTS)) == (13530, 2, 14)
+    live = [p for p, a in zip(D.PHASES, D.attrs) if not a & SKIP]
+    assert set(live) == {0, 2, 4, 6} and D.PHASES[0] == 0  # every phase, not on the first tensor
+    assert all(p == 0 for p, a in zip(D.PHASES, D.attrs) if a & SKIP)
+    # a tensor at an odd offset whose base is 8-B addressable all the same
+    i = D.names.index("l4.weight")
+    assert D.offsets[i] % 4 == 3 and D.PHASES[i] == 0
+
+
+# --------------------------------------------- table D at the instance tests' grid
+@pytest.mark.parametrize("mode", list(MODES))
+@pytest.mark.parametrize("depth", DEPTHS)
+def test_table_d_reaches_every_path_at_the_tests_grid(depth, mode):
+    it = LR.classify(D.offsets, D.numels, D.attrs, MODES[mode], D.n, D.BLOCKS, depth)
+    # the cursor is carried between full iterations of one workgroup
+    assert any(sum(1 for i in it if i.wg == w and i.full) >= 2 for w in range(D.BLOCKS))
+    # and from a full iteration into the guarded one
+    guarded = [i for i in it if not i.full]
+    assert len(guarded) == 1 and guarded[0].index >= 1
+    # one full iteration with vector groups and element-wise groups of every
+    # reason the mode can have: the flat gradient has one 8-B aligned base
+    # (bdl_lowp_step refuses another), so R_BASE cannot occur there
+    reasons = [LR.R_BOUNDARY, LR.R_SKIP] + ([LR.R_BASE] if mode == "bases" else [])
+    rich = [i for i in it if i.full and i.has(VEC) and all(i.has(ELEM, r) for r in reasons)]
+    assert rich and rich[0].gb <= 512 < rich[0].gb + 256 * depth  # elements [2048, 3072)
+    if mode == "flat":
+        assert not any(i.has(ELEM, LR.R_BASE) for i in it)
+    else:  # every odd phase is read element by element in a full iteration
+        ends = np.cumsum(D.numels)
+        for t, p in enumerate(D.PHASES):
+            if p:
+                g = (D.offsets[t] + 3) // 4  # the tensor's first whole group
+                own = [i for i in it if i.full and i.gb <= g < i.gb + i.kind.size]
+                assert own and own[0].reason[g - own[0].gb] & LR.R_BASE, (t, p)
+                assert ends[t] - D.offsets[t] >= 8
+    # the guarded iteration holds all three kinds, an odd boundary, a SKIP run and the tail
+    g = guarded[0]
+    assert g.has(VEC) and g.has(ELEM) and g.has(NONE)
+    assert g.has(ELEM, LR.R_BOUNDARY) and g.has(ELEM, LR.R_SKIP) and g.has(ELEM, LR.R_TAIL)
+    assert sum(int(((i.reason & LR.R_TAIL) != 0).sum()) for i in it) == 1
+    # every group exactly once
+    seen = np.concatenate([i.gb + np.flatnonzero(i.kind != NONE) for i in it])
+    assert sorted(seen.tolist()) == list(range((D.n + 3) // 4))
+
+
+@pytest.mark.parametrize("depth", DEPTHS)
+def test_default_grids_give_every_workgroup_one_iteration(depth):
+    """blocks = 0 on these tables (256 CUs or more, 2 workgroups per CU): as
+    many workgroups as iterations, so no cursor is carried there — why the
+    instance tests also run a literal grid of 2."""
+    for n in (D.n, int(sum(k for _, k in SEGMENTS))):
+        grid = LR.default_grid(n, depth, 256)
+        it = LR.classify([0], [n], [PRIOR], None, n, grid, depth)
+        assert len(it) == grid and all(i.index == 0 for i in it)
+
+
+def test_the_older_table_misses_the_combined_condition():
+    """Why table D exists: on the 39,426-element table the only run boundary
+    that is no multiple of 4 (16,295) and the frozen tensor never share an
+    iteration, at any depth."""
+    names = [nm for nm, _ in SEGMENTS]
+    numels = [k for _, k in SEGMENTS]
+    offsets = np.concatenate([[0], np.cumsum(numels)[:-1]]).astype(int).tolist()
+    attrs = LR._attrs_of(names, ("l7.weight",))
+    for depth in DEPTHS:
+        it = LR.classify(offsets, numels, attrs, None, sum(numels), 2, depth)
+        assert not any(i.has(ELEM, LR.R_BOUNDARY) and i.has(ELEM, LR.R_SKIP) for i in it if i.full)
+
+
+# -------------------------------------------------------- the adversarial sites
+def test_adversarial_sites_lie_where_the_test_says():
+    for depth in (1, 4):
+        for mode, bases in MODES.items():
+            it = LR.classify(D.offsets, D.numels, D.attrs, bases, D.n, D.BLOCKS, depth)
+
+            def at(e):
+                i = [x for x in it if x.gb <= e // 4 < x.gb + x.kind.size][0]
+                return i.full, int(i.kind[e // 4 - i.gb])
+
+            assert all(at(e) == (True, VEC) for e in D.SITE_VEC)
+            assert all(at(e) == (True, ELEM) for e in D.SITE_ELEM)
+            if mode == "bases":
+                assert all(at(e) == (True, ELEM) for e in D.SITE_ELEM_BASES)
+            assert all(at(e) == (False, VEC) for e in D.SITE_GUARDED_VEC)
+            assert all(at(e) == (False, ELEM) for e in D.SITE_GUARDED_ELEM)
+    attr = SR.element_attrs(D.numels, D.attrs)
+    sites = D.SITE_VEC + D.SITE_ELEM + D.SITE_ELEM_BASES + D.SITE_GUARDED_VEC + D.SITE_GUARDED_ELEM
+    assert len(set(sites)) == len(sites) and not (attr[sites] & SKIP).any()
+
+
+# ------------------------------------------------ tables B and C, stacked tests
+@pytest.mark.parametrize("depth", DEPTHS)
+@pytest.mark.parametrize("table", ["b", "c"])
+def test_seamless_tables_put_two_chains_into_one_wave_of_a_full_iteration(table, depth):
+    lay = {"b": ST.table_b, "c": ST.table_c}[table]()
+    segs = lay.stacked_segments()
+    o, k, a = ([s[i] for s in segs] for i in range(3))
+    it = LR.classify(o, k, a, None, lay.n, LR.STACKED_BLOCKS, depth)
+    split = [i for i in it if i.full and LR.waves_in_two_chains(i, lay.chain_groups)]
+    assert split, (table, depth)
+    # those waves take the vector path: the seam is no kElem group
+    for i in split:
+        for w in LR.waves_in_two_chains(i, lay.chain_groups):
+            assert (i.kind[64 * w:64 * w + 64] == VEC).all()
+    assert lay.chain_groups % 64  # a seam never falls on a wave boundary
+    assert any(sum(1 for i in it if i.wg == w and i.full) >= 2 for w in range(LR.STACKED_BLOCKS))
+
+
+# ------------------------------------------------------------ the built instances
+def test_the_library_holds_exactly_the_instances_the_matrix_launches():
+    """Names only: the set of bdl_lowp_kernel<method, noise, collect, unroll>
+    in the built library equals the instance tests' matrix, so a newly built
+    instance cannot go untested (nor a tested one vanish)."""
+    from bayesdll_amd import _lib as L
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or "/opt/rocm/llvm/bin/llvm-nm"
+    assert os.path.exists(L.LIB_PATH), "build the library first"
+    out = subprocess.run([nm, "-C", L.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    built = {tuple(int(x) for x in m.groups())
+             for m in re.finditer(r"bdl_lowp_kernel<(\d+), (\d+), (\d+), (\d+)>", out)}
+    noise = {"none": L.NOISE_NONE, "buffer": L.NOISE_BUFFER, "philox": L.NOISE_PHILOX}
+    want = {(getattr(L, m.upper()), noise[nz], getattr(L, "COLLECT_" + c), u)
+            for m, nz, c, _mom in LR.INSTANCE_CASES for u in LR.UNROLLS}
+    assert built == want
+    assert len(want) == 63 and len(LR.INSTANCE_CASES) * len(LR.UNROLLS) == 99
