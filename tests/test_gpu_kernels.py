@@ -272,14 +272,16 @@ def test_posterior_sample_matches_torch_formula():
     torch.cuda.synchronize()
     assert torch.equal(out, ref)
     # Welford form and single-sample form
-    var = (m2 / 3).clamp_(min=1e-12)
     K.posterior_sample(out, m1, m2, var_mode=L.VAR_WELFORD, ratio=3.0, noise=eps)
     torch.cuda.synchronize()
-    # torch divides by the scalar as x*(1/3) on the device, the kernel as x/3:
-    # <= 1 ulp on var, compared on the whole vector
-    want = (m1 + var.sqrt() * eps).cpu().numpy().astype(np.float64)
-    got = out.cpu().numpy().astype(np.float64)
-    assert np.max(np.abs(got - want)) / np.max(np.abs(want)) < 1e-6
+    # bit for bit the host reference (tests/draw_ref.py) in the division mode
+    # the launch took: M2 * fl(1/3) under "recip" (torch on the device), M2 / 3
+    # under "true"
+    import draw_ref
+    inv = float(draw_ref.D.inv_of(3.0)) if K.DIV_MODE == "recip" else 0.0
+    want = draw_ref.draw(m1.cpu().numpy(), m2.cpu().numpy(), eps.cpu().numpy(),
+                         var_mode=draw_ref.VAR_WELFORD, ratio=3.0, inv_ratio=inv, var_floor=1e-12)
+    assert np.array_equal(out.cpu().numpy().view(np.int32), want.view(np.int32))
     K.posterior_sample(out, m1, None, var_mode=L.VAR_GIVEN, noise=eps)
     torch.cuda.synchronize()
     assert torch.equal(out, m1 + torch.full_like(m1, 1e-12).sqrt() * eps)
