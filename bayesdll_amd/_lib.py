@@ -292,6 +292,39 @@ LOWP_EXPORTS = {
                                   C.c_void_p]),
 }
 
+
+class LayerSegment(C.Structure):
+    """include/bdl_layers.h bdl_layer_segment (a row of the device table: two int64)."""
+    _fields_ = [("offset", C.c_int64), ("numel", C.c_int64)]
+
+
+class DiagLayersArgs(C.Structure):
+    """include/bdl_layers.h bdl_diag_layers_args."""
+    _fields_ = [("mom1", _fp), ("mom2", _fp), ("segments", _fp), ("table", _fp),
+                ("workspace", _fp), ("n", C.c_int64), ("chain_groups", C.c_uint64),
+                ("nsegments", C.c_int32), ("chains", C.c_int32), ("var_mode", C.c_int32),
+                ("grid_blocks", C.c_int32), ("ratio", C.c_float), ("inv_ratio", C.c_float),
+                ("var_floor", C.c_float), ("c1", C.c_float), ("thresholds", C.c_float * 3),
+                ("pad0", C.c_int32)]
+
+
+class EssLayersArgs(C.Structure):
+    """include/bdl_layers.h bdl_ess_layers_args."""
+    _fields_ = [("sM2", _fp), ("bM2", _fp), ("segments", _fp), ("table", _fp),
+                ("workspace", _fp), ("n", C.c_int64), ("chain_groups", C.c_uint64),
+                ("samples", C.c_int64), ("batches", C.c_int64), ("nsegments", C.c_int32),
+                ("chains", C.c_int32), ("grid_blocks", C.c_int32), ("thresholds", C.c_float * 3)]
+
+
+LAYERS_MAX_SEGMENTS, LAYERS_MAX_GRID = 65536, 1024
+
+# include/bdl_layers.h: additive to the ABI, as DIAG_EXPORTS
+LAYERS_EXPORTS = {
+    "bdl_layers_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "bdl_chain_diag_layers": (C.c_int, [C.POINTER(DiagLayersArgs), C.c_void_p]),
+    "bdl_chain_ess_layers": (C.c_int, [C.POINTER(EssLayersArgs), C.c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -314,7 +347,8 @@ def lib():
                                       + list(CHAIN_STEP_EXPORTS.items())
                                       + list(STATS_EXPORTS.items())
                                       + list(ESS_EXPORTS.items())
-                                      + list(LOWP_EXPORTS.items())):
+                                      + list(LOWP_EXPORTS.items())
+                                      + list(LAYERS_EXPORTS.items())):
                 fn = getattr(h, name)
                 fn.restype = res
                 fn.argtypes = argt

@@ -6,13 +6,13 @@
 // (non-temporal 16-B loads, the chain loop unrolled by 4 so eight loads are in
 // flight per lane), then finishes its four elements (six IEEE divisions and a
 // square root per element, none per chain) and stores the requested outputs.
-// The summary's reduction is bdl_chain_common.hpp's (shared with bdl_ess.hip):
+// The per-element arithmetic is bdl_chain_elem.hpp's (shared with bdl_layers.hip), the
+// summary's reduction bdl_chain_common.hpp's (shared with bdl_ess.hip):
 // per-lane accumulators, a 64-lane butterfly, the block's 4 waves through LDS,
 // one partial per workgroup written with ordinary stores, and a one-workgroup
 // launch that combines the partials in a fixed order.  No atomics, no host
 // synchronisation, no allocation.
-#include "bdl_chain_common.hpp"
-#include "bdl_diag.h"
+#include "bdl_chain_elem.hpp"
 
 namespace bdl {
 namespace {
@@ -35,80 +35,7 @@ struct DArgs {
   float thr0, thr1, thr2;
 };
 
-using Stat = Extreme<true>;  // of rhat: every evaluated one is >= 0
-
-// bdl_diag_summary <-> Stat
-struct DiagSummary {
-  static constexpr bool kMax = true;
-  static __device__ __forceinline__ Stat load(const bdl_diag_summary& p) {
-    Stat s;
-    s.n_eval = p.n_eval;
-    s.n_deg = p.n_degenerate;
-    s.n_nonf = p.n_nonfinite;
-    s.hit0 = p.n_above[0];
-    s.hit1 = p.n_above[1];
-    s.hit2 = p.n_above[2];
-    s.arg = p.argmax;
-    s.sum = p.rhat_sum;
-    s.ext = p.rhat_max;
-    return s;
-  }
-  static __device__ __forceinline__ void store(bdl_diag_summary* __restrict__ out, const Stat& s) {
-    out->n_eval = s.n_eval;
-    out->n_degenerate = s.n_deg;
-    out->n_nonfinite = s.n_nonf;
-    out->argmax = s.arg;
-    out->n_above[0] = s.hit0;
-    out->n_above[1] = s.hit1;
-    out->n_above[2] = s.hit2;
-    out->rhat_sum = s.sum;
-    out->rhat_max = s.ext;
-    out->pad = 0.0f;
-  }
-};
-
-// One chain's contribution to a group's running sums (include/bdl_diag.h).
-template <int VAR, bool RECIP>
-__device__ __forceinline__ void accum4(const DArgs& a, const f4v m0, const f4v m, const f4v q,
-                                       f4v& S1, f4v& S2, f4v& SW) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float d = m[j] - m0[j];
-    S1[j] = S1[j] + d;
-    const float t = d * d;
-    S2[j] = S2[j] + t;
-    SW[j] = SW[j] + posterior_var<VAR, RECIP>(m[j], q[j], a.ratio, a.inv_ratio, a.var_floor);
-  }
-}
-
-// One element from its sums: outputs and the lane's statistics.
-__device__ __forceinline__ void finish_elem(const DArgs& a, float m0, float S1, float S2, float SW,
-                                            int64_t idx, float& pm, float& pv, float& rh, Stat& s) {
-  const float q = S1 / a.fk;
-  pm = m0 + q;
-  const float p = S1 * S1;
-  const float r = p / a.fk;
-  const float u = S2 - r;
-  const float ss = u < 0.0f ? 0.0f : u;
-  const float Bn = ss / a.fkm1;
-  const float W = SW / a.fk;
-  const float wa = W * a.c1;
-  const float b = wa + Bn;
-  const float c = b / W;
-  const float rhat = sqrtf(c);
-  const float e = ss / a.fk;
-  pv = W + e;
-  if (S2 == 0.0f) {
-    rh = __builtin_nanf("");
-    ++s.n_deg;
-  } else {
-    rh = rhat;
-    if (!__builtin_isfinite(rhat))
-      ++s.n_nonf;
-    else
-      count_value(s, rhat, idx, a.thr0, a.thr1, a.thr2);
-  }
-}
+using Stat = DiagStat;  // bdl_chain_elem.hpp: the adapter DiagSummary, diag_accum4, diag_finish_elem
 
 // Float4 group gi of every chain.  GUARD: the group may be the partial last
 // one (elements >= n neither read, written nor counted).
@@ -119,7 +46,7 @@ __device__ __forceinline__ void diag_group(const DArgs& a, int64_t gi, Stat& s) 
   const f4v m0 = gload<GUARD>(a.mom1, e, a.n);
   const f4v q0 = gload<GUARD>(a.mom2, e, a.n);
   f4v S1 = z, S2 = z, SW = z;
-  accum4<VAR, RECIP>(a, m0, m0, q0, S1, S2, SW);
+  diag_accum4<VAR, RECIP>(a, m0, m0, q0, S1, S2, SW);
   int k = 1;
   for (; k + 4 <= a.chains; k += 4) {
     f4v m[4], q[4];
@@ -130,20 +57,20 @@ __device__ __forceinline__ void diag_group(const DArgs& a, int64_t gi, Stat& s) 
       q[u] = gload<GUARD>(a.mom2 + o, e, a.n);
     }
 #pragma unroll
-    for (int u = 0; u < 4; ++u) accum4<VAR, RECIP>(a, m0, m[u], q[u], S1, S2, SW);
+    for (int u = 0; u < 4; ++u) diag_accum4<VAR, RECIP>(a, m0, m[u], q[u], S1, S2, SW);
   }
   for (; k < a.chains; ++k) {
     const int64_t o = (int64_t)k * a.slot;
     const f4v m = gload<GUARD>(a.mom1 + o, e, a.n);
     const f4v q = gload<GUARD>(a.mom2 + o, e, a.n);
-    accum4<VAR, RECIP>(a, m0, m, q, S1, S2, SW);
+    diag_accum4<VAR, RECIP>(a, m0, m, q, S1, S2, SW);
   }
   f4v pm = z, pv = z, rh = z;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if (GUARD && e + j >= a.n) break;
     float xm, xv, xr;
-    finish_elem(a, m0[j], S1[j], S2[j], SW[j], e + j, xm, xv, xr, s);
+    diag_finish_elem(a, m0[j], S1[j], S2[j], SW[j], e + j, xm, xv, xr, s);
     pm[j] = xm;
     pv[j] = xv;
     rh[j] = xr;

@@ -9,13 +9,13 @@
 // elements and walks the chains, K read streams a chain slot apart (chain 0
 // peeled, the loop unrolled by 4 so eight loads are in flight per lane), then
 // finishes its four elements (four IEEE divisions and a square root per
-// element, none per chain).  Its summary is reduced by bdl_chain_common.hpp
+// element, none per chain; bdl_chain_elem.hpp, shared with bdl_layers.hip).
+// Its summary is reduced by bdl_chain_common.hpp
 // (shared with bdl_diag.hip): per-lane accumulators, a 64-lane butterfly, the
 // block's 4 waves through LDS, one partial per workgroup written with ordinary
 // stores, and a one-workgroup launch that combines the partials in a fixed
 // order.  No atomics, no host synchronisation, no allocation.
-#include "bdl_chain_common.hpp"
-#include "bdl_ess.h"
+#include "bdl_chain_elem.hpp"
 
 namespace bdl {
 namespace {
@@ -140,66 +140,7 @@ struct EArgs {
   float thr0, thr1, thr2;
 };
 
-using Stat = Extreme<false>;  // of ess: every evaluated one is finite
-
-// bdl_ess_summary <-> Stat
-struct EssSummary {
-  static constexpr bool kMax = false;
-  static __device__ __forceinline__ Stat load(const bdl_ess_summary& p) {
-    Stat s;
-    s.n_eval = p.n_eval;
-    s.n_deg = p.n_degenerate;
-    s.n_nonf = p.n_nonfinite;
-    s.hit0 = p.n_below[0];
-    s.hit1 = p.n_below[1];
-    s.hit2 = p.n_below[2];
-    s.arg = p.argmin;
-    s.sum = p.ess_sum;
-    s.ext = p.ess_min;
-    return s;
-  }
-  static __device__ __forceinline__ void store(bdl_ess_summary* __restrict__ out, const Stat& s) {
-    out->n_eval = s.n_eval;
-    out->n_degenerate = s.n_deg;
-    out->n_nonfinite = s.n_nonf;
-    out->argmin = s.arg;
-    out->n_below[0] = s.hit0;
-    out->n_below[1] = s.hit1;
-    out->n_below[2] = s.hit2;
-    out->ess_sum = s.sum;
-    out->ess_min = s.ext;
-    out->pad = 0.0f;
-  }
-};
-
-__device__ __forceinline__ void accum4(const f4v m, const f4v q, f4v& SW, f4v& SV) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    SW[j] = SW[j] + m[j];
-    SV[j] = SV[j] + q[j];
-  }
-}
-
-// One element from its sums: outputs and the lane's statistics.
-__device__ __forceinline__ void finish_elem(const EArgs& a, float SW, float SV, int64_t idx,
-                                            float& es, float& mc, Stat& s) {
-  const float w = SW / a.fS1;
-  const float v = SV / a.fnb1;
-  const float r = w / v;
-  const float ess = r * a.fKnb;
-  const float g = v / a.fKnb;
-  mc = sqrtf(g);
-  if (SV == 0.0f) {
-    es = __builtin_nanf("");
-    ++s.n_deg;
-  } else {
-    es = ess;
-    if (!__builtin_isfinite(ess))
-      ++s.n_nonf;
-    else
-      count_value(s, ess, idx, a.thr0, a.thr1, a.thr2);
-  }
-}
+using Stat = EssStat;  // bdl_chain_elem.hpp: the adapter EssSummary, ess_accum4, ess_finish_elem
 
 // Float4 group gi of every chain.  GUARD: the group may be the partial last
 // one (elements >= n neither read, written nor counted).
@@ -210,7 +151,7 @@ __device__ __forceinline__ void ess_group(const EArgs& a, int64_t gi, Stat& s) {
   const f4v m0 = gload<GUARD>(a.sM2, e, a.n);
   const f4v q0 = gload<GUARD>(a.bM2, e, a.n);
   f4v SW = z, SV = z;
-  accum4(m0, q0, SW, SV);
+  ess_accum4(m0, q0, SW, SV);
   int k = 1;
   for (; k + 4 <= a.chains; k += 4) {
     f4v m[4], q[4];
@@ -221,20 +162,20 @@ __device__ __forceinline__ void ess_group(const EArgs& a, int64_t gi, Stat& s) {
       q[u] = gload<GUARD>(a.bM2 + o, e, a.n);
     }
 #pragma unroll
-    for (int u = 0; u < 4; ++u) accum4(m[u], q[u], SW, SV);
+    for (int u = 0; u < 4; ++u) ess_accum4(m[u], q[u], SW, SV);
   }
   for (; k < a.chains; ++k) {
     const int64_t o = (int64_t)k * a.slot;
     const f4v m = gload<GUARD>(a.sM2 + o, e, a.n);
     const f4v q = gload<GUARD>(a.bM2 + o, e, a.n);
-    accum4(m, q, SW, SV);
+    ess_accum4(m, q, SW, SV);
   }
   f4v es = z, mc = z;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if (GUARD && e + j >= a.n) break;
     float xe, xm;
-    finish_elem(a, SW[j], SV[j], e + j, xe, xm, s);
+    ess_finish_elem(a, SW[j], SV[j], e + j, xe, xm, s);
     es[j] = xe;
     mc[j] = xm;
   }

@@ -11,6 +11,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -683,6 +684,109 @@ def chain_ess(sM2, bM2, *, chains, chain_groups, n, samples, batches,
     ev = torch.cuda.Event()
     ev.record(torch.cuda.current_stream(dev))
     return EssResult(outs, snap, ev, thresholds)
+
+
+def _layers_call(what, vectors, segments, *, chains, chain_groups, n, grid_blocks, chains_error,
+                 summary_type):
+    """What chain_diag_layers / chain_ess_layers share: the layout checks, the
+    segment table's shape, the grid (0: two workgroups per CU), the workspace
+    and the output table.  Returns (chains, chain_groups, n, device, nsegments,
+    grid, workspace, table)."""
+    chains, chain_groups, n, dev = _stacked_layout(what, vectors, chains, chain_groups, n,
+                                                   chains_error=chains_error)
+    if (not torch.is_tensor(segments) or segments.dtype != torch.int64 or segments.dim() != 2
+            or segments.shape[1] != 2 or not segments.is_contiguous()):
+        raise ValueError(f"{what}: segments must be a contiguous int64 [nsegments, 2] tensor of "
+                         "(offset, numel) rows")
+    if segments.device != dev:
+        raise ValueError(f"{what}: segments must be on the vectors' device")
+    nseg = int(segments.shape[0])
+    if not 1 <= nseg <= L.LAYERS_MAX_SEGMENTS:
+        raise ValueError(f"{what}: 1 <= nsegments <= {L.LAYERS_MAX_SEGMENTS} is required")
+    grid = int(grid_blocks)
+    if not 0 <= grid <= L.LAYERS_MAX_GRID:
+        raise ValueError(f"{what}: grid_blocks in [0, {L.LAYERS_MAX_GRID}]")
+    if grid == 0:
+        grid = max(1, min(2 * torch.cuda.get_device_properties(dev).multi_processor_count,
+                          L.LAYERS_MAX_GRID))
+    nbytes = int(L.lib().bdl_layers_workspace_bytes(nseg, grid))
+    ws = _scratch(("layers", dev.index, nbytes),
+                  lambda: torch.empty(nbytes, dtype=torch.uint8, device=dev))
+    table = torch.empty(nseg * C.sizeof(summary_type), dtype=torch.uint8, device=dev)
+    return chains, chain_groups, n, dev, nseg, grid, ws, table
+
+
+def _layers_table(table, summary_type):
+    """The device table as a structured host array (one wait: the copy)."""
+    return np.frombuffer(table.cpu().numpy().tobytes(), dtype=np.dtype(summary_type))
+
+
+def chain_diag_layers(mom1, mom2, segments, *, chains, chain_groups, n, var_mode, ratio, count,
+                      var_floor=1e-12, thresholds=(1.01, 1.05, 1.1), grid_blocks=0, div_mode=None):
+    """Per-tensor R-hat of `chains` stacked chains (bdl_chain_diag_layers,
+    include/bdl_layers.h): chain_diag's inputs and a device table of
+    (chain-local offset, numel) rows, one per tensor.  Row t of the result is
+    the summary chain_diag would report if only tensor t's elements existed
+    (argmax chain-local), as a structured host array with bdl_diag_summary's
+    fields.  One sweep and a per-segment combine on the current stream, then
+    one wait for the table; no per-element output.  Counts, rhat_max and
+    argmax never depend on grid_blocks (workgroups of the sweep, 0: default)."""
+    if mom2 is None:
+        raise ValueError("chain_diag_layers: the second moment is required (mom2 is None)")
+    if mom1 is None:
+        raise ValueError("chain_diag_layers: mom1 is required")
+    if int(count) < 2:
+        raise ValueError("chain_diag_layers: R-hat needs at least 2 samples per chain "
+                         f"(count = {count})")
+    if len(thresholds) != 3:
+        raise ValueError("chain_diag_layers: three thresholds")
+    chains, chain_groups, n, dev, nseg, grid, ws, table = _layers_call(
+        "chain_diag_layers", (("mom1", mom1), ("mom2", mom2)), segments, chains=chains,
+        chain_groups=chain_groups, n=n, grid_blocks=grid_blocks, summary_type=L.DiagSummary,
+        chains_error=lambda k: f"at least 2 chains are required (chains = {k})" if k < 2 else None)
+    a = L.DiagLayersArgs()
+    a.mom1, a.mom2 = mom1.data_ptr(), mom2.data_ptr()
+    a.segments, a.table, a.workspace = segments.data_ptr(), table.data_ptr(), ws.data_ptr()
+    a.n, a.chain_groups, a.nsegments, a.chains = n, chain_groups, nseg, chains
+    a.var_mode, a.grid_blocks = int(var_mode), grid
+    a.ratio = float(ratio)
+    a.inv_ratio = _inv(ratio) if _div_flag(div_mode) else 0.0  # as chain_diag
+    a.var_floor = float(var_floor)
+    a.c1 = (int(count) - 1) / int(count)
+    for i, t in enumerate(thresholds):
+        a.thresholds[i] = float(t)
+    L.check(L.lib().bdl_chain_diag_layers(a, L.current_stream_handle(dev)),
+            "bdl_chain_diag_layers")
+    return _layers_table(table, L.DiagSummary)
+
+
+def chain_ess_layers(sM2, bM2, segments, *, chains, chain_groups, n, samples, batches,
+                     thresholds=E.DEFAULT_THRESHOLDS, grid_blocks=0):
+    """Per-tensor batch-means effective sample size of `chains` stacked chains
+    (bdl_chain_ess_layers, include/bdl_layers.h): chain_ess's inputs and the
+    segment table of chain_diag_layers.  Row t of the result is the summary
+    chain_ess would report if only tensor t's elements existed (argmin
+    chain-local), as a structured host array with bdl_ess_summary's fields.
+    chains = 1 on one chain's slice reports that chain alone.  One sweep and a
+    per-segment combine on the current stream, then one wait for the table."""
+    samples, batches = int(samples), int(batches)
+    if samples < 2 or batches < 2:
+        raise ValueError("chain_ess_layers: at least 2 samples and 2 closed batches are required "
+                         f"(samples = {samples}, batches = {batches})")
+    thresholds = E.thresholds(thresholds)
+    chains, chain_groups, n, dev, nseg, grid, ws, table = _layers_call(
+        "chain_ess_layers", (("sM2", sM2), ("bM2", bM2)), segments, chains=chains,
+        chain_groups=chain_groups, n=n, grid_blocks=grid_blocks, summary_type=L.EssSummary,
+        chains_error=None)
+    a = L.EssLayersArgs()
+    a.sM2, a.bM2 = sM2.data_ptr(), bM2.data_ptr()
+    a.segments, a.table, a.workspace = segments.data_ptr(), table.data_ptr(), ws.data_ptr()
+    a.n, a.chain_groups, a.nsegments, a.chains = n, chain_groups, nseg, chains
+    a.samples, a.batches, a.grid_blocks = samples, batches, grid
+    for i, t in enumerate(thresholds):
+        a.thresholds[i] = t
+    L.check(L.lib().bdl_chain_ess_layers(a, L.current_stream_handle(dev)), "bdl_chain_ess_layers")
+    return _layers_table(table, L.EssSummary)
 
 
 def clip_bytes_per_elem(clipped_share=1.0):

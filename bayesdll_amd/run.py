@@ -132,7 +132,22 @@ def build_parser():
                          "batch-means accumulators (batches of B samples) and log the effective "
                          "sample size of the latest component at every evaluation (stacked "
                          "ess()); per chain with --sweep")
+    ap.add_argument("--by_tensor", type=int, default=0, metavar="N",
+                    help="with --rhat and / or --ess: after their log line, also log the N "
+                         "tensors with the largest R-hat maximum and the N with the smallest "
+                         "ESS minimum (one fused per-tensor sweep each, by_tensor=True), and "
+                         "keep the whole per-tensor table in the epoch record")
     return ap
+
+
+def check_by_tensor(ap, args):
+    """--by_tensor N needs N >= 0 and --rhat or --ess (ap.error otherwise)."""
+    if args.by_tensor < 0:
+        ap.error("--by_tensor: N must be >= 0")
+    if args.by_tensor and not (args.rhat or args.ess):
+        ap.error("--by_tensor lists the tensors of the R-hat / ESS reports: it needs --rhat "
+                 "or --ess")
+    return args.by_tensor
 
 
 def check_ess(ap, args):
@@ -246,6 +261,7 @@ def main(argv=None):
     sweep = parse_sweep(ap, args)
     check_health(ap, args)
     check_ess(ap, args)
+    check_by_tensor(ap, args)
     check_compute_dtype(ap, args)
     from . import chains
     rank, world, device = chains.init_chains()

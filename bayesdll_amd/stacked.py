@@ -164,6 +164,7 @@ class StackedState:
         self.grad, self.gbase, self._tables = None, None, {}
         self._gbound, self._seg_tables = None, {}  # grad_segments: what use_grads bound last
         self._stat_tables = {}                     # stat_segments, per bound gradient set
+        self._layer_table = None                   # layer_segments: built once
         self.chain_runs, self.chain_nruns, self.chain_gbase = None, 0, None
         if self.chain_tables:
             # one run per tensor whatever K is: the in-place form serves any K
@@ -315,6 +316,17 @@ class StackedState:
             return _upload_table(self.device, rows).view(len(rows), 5), len(rows), tuple(idx)
 
         return _cached_table(self._stat_tables, key, build)
+
+    def layer_segments(self):
+        """The device table of kernels.chain_diag_layers / chain_ess_layers: one
+        (chain-local offset, numel) int64 row per tensor of `names`, in
+        parameter order, frozen tensors included (include/bdl_layers.h); a
+        chain's padding lies in no row.  It depends on nothing that changes:
+        built once."""
+        if self._layer_table is None:
+            rows = list(zip(self.offsets, self.numels))
+            self._layer_table = _upload_table(self.device, rows).view(len(rows), 2)
+        return self._layer_table
 
     def diverged(self, reset=True):
         bad = bool(self.nonfinite.any().item())
@@ -522,7 +534,7 @@ class _StackedSampler:
                    chain_groups=st.chain_groups, n=st.n1, sample=e[1] + 1, batch=self.ess_batch)
         e[1] += 1
 
-    def ess(self, *, by_chain=False, ess=False, mcse=False, thresholds=None):
+    def ess(self, *, by_chain=False, ess=False, mcse=False, thresholds=None, by_tensor=False):
         """How many independent samples do the collected samples of the latest
         component stand for?  The batch-means effective sample size per
         element, pooled over the K chains the way R-hat pools the within-chain
@@ -538,6 +550,12 @@ class _StackedSampler:
         mcse / sqrt(K)).  by_chain=True: a list of K such results, chain k's from its own
         accumulators alone (K launches) — the only form under per_chain
         hyperparameters, whose chains target different posteriors.
+        by_tensor=True: the result gains `by_tensor`, a list in parameter
+        order of {name, numel, n_eval, n_degenerate, n_nonfinite, ess_min,
+        argmin (chain-local, as the summary's), ess_mean, n_below,
+        share_below} — the summary of each tensor alone, from one more fused
+        sweep (kernels.chain_ess_layers) with no per-element output; with
+        by_chain each of the K results carries its own table.
 
         The accumulators count true samples (no double count, no burn-in
         seed), restart at a component's init collect, are no part of
@@ -561,25 +579,32 @@ class _StackedSampler:
                               thresholds=thr, want=want)
             return res
 
-        def finish(res, chains):
+        def finish(res, chains, sl):
             out = ESS.summary_dict(res.summary, thr, samples=S_, batches=nb,
                                    batch=self.ess_batch, chains=chains)
             out["component"] = comp
             out["argmin_param"] = self.param_of(out["argmin"]) if out["argmin"] >= 0 else None
             out.update({w: res[w] for w in want})
+            if by_tensor:
+                tab = K.chain_ess_layers(v["sM2"][sl:], v["bM2"][sl:], st.layer_segments(),
+                                         chains=chains, chain_groups=st.chain_groups, n=st.n1,
+                                         samples=S_, batches=nb, thresholds=thr)
+                out["by_tensor"] = self._tensor_rows(tab, "ess_min", "argmin", "n_below",
+                                                     "ess_mean", "share_below")
             return out
 
         if not by_chain:
-            return finish(report(0, self.K), self.K)
+            return finish(report(0, self.K), self.K, 0)
         launched = [report(k * st.stride, 1) for k in range(self.K)]  # K launches, then one wait
-        return [finish(r, 1) for r in launched]
+        return [finish(r, 1, k * st.stride) for k, r in enumerate(launched)]
 
     def _report_ess(self, ep, rec, log):
         """One log line (one per chain under per_chain) and rec["ess"] from
         `ess()` (run.py --ess); an evaluation that comes before two batches are
         closed says so and goes on."""
         try:
-            d = self.ess(by_chain=self.per_chain is not None)
+            d = self.ess(by_chain=self.per_chain is not None,
+                         **({"by_tensor": True} if self._by_tensor() else {}))
         except ValueError as e:
             log(f"(Epoch {ep}) ESS: {e}")
             return
@@ -595,6 +620,24 @@ class _StackedSampler:
                 f"({r['argmin_param']}), mean = {r['ess_mean']:.1f}, {shares}; "
                 f"{r['n_eval']} evaluated, {r['n_degenerate']} degenerate, "
                 f"{r['n_nonfinite']} non-finite")
+            self._log_tensors(ep, log, f"ESS {who}", r, "ess_min", "ess_mean", "share_below",
+                              "<", ".1f", worst=min)
+
+    def _by_tensor(self):
+        """How many tensors the reports list (run.py --by_tensor N; 0: none)."""
+        return int(getattr(self.args, "by_tensor", 0) or 0)
+
+    def _log_tensors(self, ep, log, what, r, ext, mean, share, sign, fmt, worst):
+        """One log line per tensor for the --by_tensor N worst tensors of a
+        report `r` that carries `by_tensor`: those with the largest rhat_max /
+        smallest ess_min among the tensors with something evaluated."""
+        n = self._by_tensor()
+        rows = [t for t in r.get("by_tensor", ()) if t["n_eval"] > 0]
+        rows.sort(key=lambda t: t[ext], reverse=worst is max)
+        for t in rows[:n]:
+            log(f"(Epoch {ep}) {what}, tensor {t['name']} ({t['numel']} elements): "
+                f"{worst.__name__} = {t[ext]:{fmt}}, mean = {t[mean]:{fmt}}, "
+                f"{sign} {r['thresholds'][0]:g}: {100 * t[share][0]:.1f} %")
 
     # --------------------------------------------------------------- health
     def _health_lr(self, lrs, collect=None, rows=None):
@@ -863,13 +906,28 @@ class _StackedSampler:
         not collected; m2 None: the second moment is not kept / not used)."""
         raise NotImplementedError
 
+    def _tensor_rows(self, table, ext, arg, hits, mean, share):
+        """A per-tensor device table (kernels.chain_*_layers) as a list of
+        dicts in parameter order; ext / arg / hits name the struct's fields,
+        mean / share the derived keys (ext's own name prefixes sum and mean)."""
+        st, rows = self.state, []
+        for nm, numel, r in zip(st.names, st.numels, table):
+            ne, hit = int(r["n_eval"]), [int(v) for v in r[hits]]
+            rows.append({"name": nm, "numel": int(numel), "n_eval": ne,
+                         "n_degenerate": int(r["n_degenerate"]),
+                         "n_nonfinite": int(r["n_nonfinite"]), ext: float(r[ext]),
+                         arg: int(r[arg]),
+                         mean: float(r[ext.split("_")[0] + "_sum"]) / ne if ne else float("nan"),
+                         hits: hit, share: [v / ne if ne else float("nan") for v in hit]})
+        return rows
+
     def param_of(self, index):
         """Name of the parameter tensor holding flat element `index` of a chain."""
         st = self.state
         i = int(np.searchsorted(np.asarray(st.offsets), int(index), side="right")) - 1
         return st.names[max(i, 0)]
 
-    def diagnostics(self, component=None, *, rhat=False, pooled=False):
+    def diagnostics(self, component=None, *, rhat=False, pooled=False, by_tensor=False):
         """Do the K chains agree?  The cross-chain Gelman-Rubin R-hat and the
         pooled Gaussian posterior of a collected component (default: the
         latest), from the chains' moments in one fused sweep
@@ -877,7 +935,12 @@ class _StackedSampler:
         n_nonfinite, rhat_max, argmax and its parameter name, rhat_mean,
         n_above / share_above the thresholds 1.01 / 1.05 / 1.1, count,
         component) plus, when asked for, the [n1] tensors `rhat` and
-        `pooled_mean` / `pooled_var`.  Reads the moments only: nothing the
+        `pooled_mean` / `pooled_var`.  by_tensor=True: the result gains
+        `by_tensor`, a list in parameter order of {name, numel, n_eval,
+        n_degenerate, n_nonfinite, rhat_max, argmax (chain-local, as the
+        summary's), rhat_mean, n_above, share_above} — the summary of each
+        tensor alone, from one more fused sweep (kernels.chain_diag_layers)
+        with no per-element output.  Reads the moments only: nothing the
         sampler owns is written."""
         if self.K < 2:
             raise ValueError("diagnostics: R-hat compares chains; this sampler runs K = 1")
@@ -907,6 +970,12 @@ class _StackedSampler:
         out["component"], out["count"] = component, int(count)
         out["argmax_param"] = self.param_of(out["argmax"]) if out["argmax"] >= 0 else None
         out.update({w: res[w] for w in want})
+        if by_tensor:
+            tab = K.chain_diag_layers(m1, m2, st.layer_segments(), chains=self.K,
+                                      chain_groups=st.chain_groups, n=st.n1, var_mode=var_mode,
+                                      ratio=ratio, count=count)
+            out["by_tensor"] = self._tensor_rows(tab, "rhat_max", "argmax", "n_above", "rhat_mean",
+                                                 "share_above")
         return out
 
     def evaluate(self, loader):
@@ -1025,7 +1094,7 @@ class _StackedSampler:
         """One log line and rec["rhat"] from `diagnostics()`; an evaluation
         that comes before the diagnostic is defined says so and goes on."""
         try:
-            d = self.diagnostics()
+            d = self.diagnostics(**({"by_tensor": True} if self._by_tensor() else {}))
         except ValueError as e:
             log(f"(Epoch {ep}) R-hat: {e}")
             return
@@ -1036,6 +1105,8 @@ class _StackedSampler:
             f"({d['count']} samples each): max = {d['rhat_max']:.4f} ({d['argmax_param']}), "
             f"mean = {d['rhat_mean']:.4f}, {shares}; {d['n_eval']} evaluated, "
             f"{d['n_degenerate']} degenerate, {d['n_nonfinite']} non-finite")
+        self._log_tensors(ep, log, f"R-hat over {self.K} chains", d, "rhat_max", "rhat_mean",
+                          "share_above", ">", ".4f", worst=max)
 
 
 class StackedCSGHMC(_StackedSampler):
