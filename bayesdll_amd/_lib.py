@@ -325,6 +325,39 @@ LAYERS_EXPORTS = {
     "bdl_chain_ess_layers": (C.c_int, [C.POINTER(EssLayersArgs), C.c_void_p]),
 }
 
+PREDICT_MAX_CLASSES, PREDICT_WAVE_CLASSES, PREDICT_MAX_BINS = 8192, 256, 64
+PREDICT_MAX_GROUPS, PREDICT_MAX_GRID = 65535, 1024
+PREDICT_RESET = 0x1
+
+
+class PredictTotals(C.Structure):
+    """include/bdl_predict.h bdl_predict_totals (one per group, device memory)."""
+    _fields_ = [("n", C.c_int64), ("n_labelled", C.c_int64), ("n_nonfinite", C.c_int64),
+                ("n_wrong", C.c_int64), ("disagree_sum", C.c_int64), ("nll_sum", C.c_double),
+                ("entropy_sum", C.c_double), ("expected_entropy_sum", C.c_double),
+                ("mi_sum", C.c_double), ("mi_sum_wrong", C.c_double),
+                ("bin_count", C.c_int64 * PREDICT_MAX_BINS),
+                ("bin_hits", C.c_int64 * PREDICT_MAX_BINS),
+                ("bin_conf", C.c_double * PREDICT_MAX_BINS)]
+
+
+class PredictArgs(C.Structure):
+    """include/bdl_predict.h bdl_predict_args."""
+    _fields_ = [("logits", _fp), ("labels", _fp), ("logp", _fp), ("entropy", _fp),
+                ("expected_entropy", _fp), ("mutual_info", _fp), ("confidence", _fp),
+                ("nll", _fp), ("pred", _fp), ("disagree", _fp), ("totals", _fp),
+                ("workspace", _fp), ("batch", C.c_int64), ("members", C.c_int32),
+                ("groups", C.c_int32), ("classes", C.c_int32), ("num_bins", C.c_int32),
+                ("grid_blocks", C.c_int32), ("flags", C.c_int32),
+                ("edges", C.c_float * PREDICT_MAX_BINS)]
+
+
+# include/bdl_predict.h: additive to the ABI, as DIAG_EXPORTS
+PREDICT_EXPORTS = {
+    "bdl_predict_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "bdl_predict": (C.c_int, [C.POINTER(PredictArgs), C.c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -348,7 +381,8 @@ def lib():
                                       + list(STATS_EXPORTS.items())
                                       + list(ESS_EXPORTS.items())
                                       + list(LOWP_EXPORTS.items())
-                                      + list(LAYERS_EXPORTS.items())):
+                                      + list(LAYERS_EXPORTS.items())
+                                      + list(PREDICT_EXPORTS.items())):
                 fn = getattr(h, name)
                 fn.restype = res
                 fn.argtypes = argt

@@ -789,6 +789,143 @@ def chain_ess_layers(sM2, bM2, segments, *, chains, chain_groups, n, samples, ba
     return _layers_table(table, L.EssSummary)
 
 
+PREDICT_OUTPUTS = ("logp", "entropy", "expected_entropy", "mutual_info", "confidence", "nll",
+                   "pred", "disagree")
+PREDICT_DEFAULT_WANT = PREDICT_OUTPUTS[1:]
+
+
+def predict_edges(num_bins):
+    """The num_bins - 1 interior right edges of calibration.calc_bins' bins, as
+    the fp32 values bdl_predict compares against."""
+    return np.linspace(0, 1 + 1e-8, int(num_bins) + 1)[1:-1].astype(np.float32)
+
+
+def predict_summary(row, members, num_bins):
+    """One group's host-read bdl_predict_totals as a dict: n, nll, error, ece /
+    mce (calibration.analyze's formula on the bins), entropy, expected_entropy,
+    mutual_info, mutual_info_wrong / mutual_info_correct (over the labelled
+    examples the vote gets wrong / over every other evaluated example),
+    disagreement (the mean share of members off the vote), bins, n_nonfinite.
+    A mean over nothing is NaN."""
+    def over(s, k):
+        return float(s) / k if k else float("nan")
+    nb = int(num_bins)
+    n, nl, nw = int(row["n"]), int(row["n_labelled"]), int(row["n_wrong"])
+    cnt = np.asarray(row["bin_count"][:nb], dtype=np.float64)
+    hits = np.asarray(row["bin_hits"][:nb], dtype=np.float64)
+    conf = np.asarray(row["bin_conf"][:nb], dtype=np.float64)
+    full = cnt > 0
+    accs = np.where(full, hits / np.where(full, cnt, 1), 0.0)
+    confs = np.where(full, conf / np.where(full, cnt, 1), 0.0)
+    gap = np.abs(accs - confs)
+    tot = cnt.sum()
+    return {"n": n, "n_labelled": nl, "n_nonfinite": int(row["n_nonfinite"]),
+            "nll": over(row["nll_sum"], nl), "error": over(nw, nl),
+            "ece": float((gap * (cnt / tot)).sum()) if tot else float("nan"),
+            "mce": float(gap.max()) if tot else float("nan"),
+            "entropy": over(row["entropy_sum"], n),
+            "expected_entropy": over(row["expected_entropy_sum"], n),
+            "mutual_info": over(row["mi_sum"], n),
+            "mutual_info_wrong": over(row["mi_sum_wrong"], nw),
+            "mutual_info_correct": over(float(row["mi_sum"]) - float(row["mi_sum_wrong"]), n - nw),
+            "disagreement": over(row["disagree_sum"], n * int(members)),
+            "bins": {"count": cnt.astype(np.int64).tolist(),
+                     "hits": hits.astype(np.int64).tolist(), "conf_sum": conf.tolist(),
+                     "accuracy": accs.tolist(), "confidence": confs.tolist()}}
+
+
+class PredictTotals:
+    """The running totals of `predict` calls: bdl_predict_totals[groups] in
+    device memory.  `read()` is the one host read (a structured array with the
+    struct's fields), `summary()` the dict(s) of predict_summary."""
+
+    def __init__(self, groups, members, num_bins, device):
+        self.groups, self.members, self.num_bins = int(groups), int(members), int(num_bins)
+        self.buf = torch.empty(self.groups * C.sizeof(L.PredictTotals), dtype=torch.uint8,
+                               device=device)
+        self.fresh = True  # nothing accumulated: the first call resets
+
+    def read(self):
+        if self.fresh:
+            raise ValueError("predict: these totals hold nothing yet")
+        return np.frombuffer(self.buf.cpu().numpy().tobytes(), dtype=np.dtype(L.PredictTotals))
+
+    def summary(self):
+        return [predict_summary(r, self.members, self.num_bins) for r in self.read()]
+
+
+def predict(logits, labels=None, *, groups=1, totals=None, reset=False, num_bins=15,
+            want=PREDICT_DEFAULT_WANT, grid_blocks=0):
+    """Predictive uncertainty and calibration of an ensemble from its member
+    logits in one fused sweep (bdl_predict, include/bdl_predict.h: the
+    definitions and the arithmetic contract).  logits: fp32, contiguous
+    [..., B, C] whose leading dimensions flatten to members x groups in that
+    order ([M, B, C] with groups=1 pools all members; [components, K, B, C]
+    with groups=K gives every chain its own mixture).  labels: int64 [B] on the
+    device or None; a label outside [0, C) leaves the example unlabelled.
+    Returns (outs, totals): outs[w] for w in want — `logp` [G, B, C], the
+    others [G, B] — and the PredictTotals handle the call ADDED to (a new one,
+    or the one passed in; reset=True overwrites it).  Two launches on the
+    current stream, no host read here: totals.read() / .summary() is the one."""
+    want = tuple(want)
+    if any(w not in PREDICT_OUTPUTS for w in want):
+        raise ValueError(f"predict: want from {PREDICT_OUTPUTS}")
+    if not torch.is_tensor(logits) or logits.dim() < 2:
+        raise ValueError("predict: logits must be a [..., B, C] tensor")
+    L.require_hip(logits, "logits")
+    if not logits.is_contiguous():
+        raise ValueError("predict: logits must be contiguous")
+    G, nb = int(groups), int(num_bins)
+    B, Cn = int(logits.shape[-2]), int(logits.shape[-1])
+    lead = logits.numel() // max(B * Cn, 1)
+    if not 1 <= G <= L.PREDICT_MAX_GROUPS or B < 1 or lead < 1 or lead % G:
+        raise ValueError(f"predict: {tuple(logits.shape)} is not members x groups ({G}) x B x C")
+    if not 1 <= Cn <= L.PREDICT_MAX_CLASSES:
+        raise ValueError(f"predict: 1 <= classes <= {L.PREDICT_MAX_CLASSES} (got {Cn})")
+    if not 1 <= nb <= L.PREDICT_MAX_BINS:
+        raise ValueError(f"predict: 1 <= num_bins <= {L.PREDICT_MAX_BINS} (got {nb})")
+    grid = int(grid_blocks)
+    if not 0 <= grid <= L.PREDICT_MAX_GRID:
+        raise ValueError(f"predict: grid_blocks in [0, {L.PREDICT_MAX_GRID}]")
+    M, dev = lead // G, logits.device
+    if labels is not None:
+        if (not torch.is_tensor(labels) or labels.dtype != torch.int64 or labels.shape != (B,)
+                or not labels.is_contiguous() or labels.device != dev):
+            raise ValueError("predict: labels must be a contiguous int64 [B] tensor on the logits' "
+                             "device")
+    if totals is None:
+        totals = PredictTotals(G, M, nb, dev)
+    elif (totals.groups, totals.members, totals.num_bins) != (G, M, nb) or totals.buf.device != dev:
+        raise ValueError("predict: these totals were started with other groups / members / "
+                         "num_bins or on another device")
+    if grid == 0:  # the library's default, so that the workspace is sized for it
+        per_group = -(-B // (4 if Cn <= L.PREDICT_WAVE_CLASSES else 1))
+        cus = torch.cuda.get_device_properties(dev).multi_processor_count
+        grid = max(1, min(min(per_group, L.PREDICT_MAX_GRID) * G, 4 * cus, L.PREDICT_MAX_GRID))
+    nbytes = int(L.lib().bdl_predict_workspace_bytes(G, grid))
+    ws = _scratch(("predict", dev.index, nbytes),
+                  lambda: torch.empty(nbytes, dtype=torch.uint8, device=dev))
+    outs = {}
+    for w in want:
+        shape = (G, B, Cn) if w == "logp" else (G, B)
+        outs[w] = torch.empty(shape, device=dev,
+                              dtype=torch.int32 if w in ("pred", "disagree") else torch.float32)
+    a = L.PredictArgs()
+    a.logits = logits.data_ptr()
+    a.labels = None if labels is None else labels.data_ptr()
+    for w in PREDICT_OUTPUTS:
+        setattr(a, w, outs[w].data_ptr() if w in outs else None)
+    a.totals, a.workspace = totals.buf.data_ptr(), ws.data_ptr()
+    a.batch, a.members, a.groups, a.classes, a.num_bins = B, M, G, Cn, nb
+    a.grid_blocks = grid
+    a.flags = L.PREDICT_RESET if (reset or totals.fresh) else 0
+    for i, e in enumerate(predict_edges(nb)):
+        a.edges[i] = float(e)
+    L.check(L.lib().bdl_predict(a, L.current_stream_handle(dev)), "bdl_predict")
+    totals.fresh = False
+    return outs, totals
+
+
 def clip_bytes_per_elem(clipped_share=1.0):
     """Algorithmic HBM bytes per gradient element of one chain_clip call
     (DESIGN §4e): every element read once for the norm; the elements of the

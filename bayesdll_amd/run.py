@@ -137,7 +137,21 @@ def build_parser():
                          "tensors with the largest R-hat maximum and the N with the smallest "
                          "ESS minimum (one fused per-tensor sweep each, by_tensor=True), and "
                          "keep the whole per-tensor table in the epoch record")
+    ap.add_argument("--uncertainty", action="store_true",
+                    help="with --stacked_chains >= 1: at every evaluation, log the stacked "
+                         "predictive's NLL, error, ECE / MCE (--ece_num_bins), total and expected "
+                         "entropy, mutual information (overall, on wrong against other examples) "
+                         "and member disagreement from one fused sweep over the members' logits "
+                         "(stacked uncertainty()); per chain with --sweep")
     return ap
+
+
+def check_uncertainty(ap, args):
+    """--uncertainty needs stacked chains (ap.error otherwise)."""
+    if args.uncertainty and args.stacked_chains < 1:
+        ap.error("--uncertainty reports the stacked chains' predictive: it needs "
+                 "--stacked_chains >= 1")
+    return args.uncertainty
 
 
 def check_by_tensor(ap, args):
@@ -261,6 +275,7 @@ def main(argv=None):
     sweep = parse_sweep(ap, args)
     check_health(ap, args)
     check_ess(ap, args)
+    check_uncertainty(ap, args)
     check_by_tensor(ap, args)
     check_compute_dtype(ap, args)
     from . import chains

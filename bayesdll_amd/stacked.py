@@ -996,6 +996,101 @@ class _StackedSampler:
             self.net.train(was)
         return loss / nb, err / nb
 
+    def _member_logits(self, x, bufs):
+        """[members, K, B, C] raw logits of the members `_component_logprobs`
+        averages over — the same draws in the same order from the same keys,
+        or the chains' current theta while nothing is collected — written into
+        one buffer per batch shape (kept in `bufs`)."""
+        st = self.state
+        n = len(self._component_keys()) * max(1, self.nst)
+        with torch.no_grad():
+            if n == 0:
+                return self.chain_logits(x).float().contiguous().unsqueeze(0)
+            buf = torch.empty_like(st.theta)
+            views = {nm: buf.view(self.K, st.stride)[:, o:o + k].view(self.K, *s)
+                     for nm, o, k, s in zip(st.names, st.offsets, st.numels, st.shapes)}
+            out = None
+            for i, _ in enumerate(self._components(buf)):
+                lg = self._fwd(views, x)
+                if out is None:
+                    key = (n,) + tuple(lg.shape)
+                    out = bufs.get(key)
+                    if out is None:
+                        out = bufs[key] = torch.empty(key, dtype=torch.float32, device=lg.device)
+                out[i].copy_(lg)
+            return out
+
+    def uncertainty(self, loader, *, by_chain=False, num_bins=None, per_example=False):
+        """What the ensemble is for, over a data loader (the network in eval
+        mode, as `evaluate`): NLL, error, ECE / MCE over `num_bins` confidence
+        bins of every (example, class) probability (default args.ece_num_bins,
+        else 15), the predictive's total entropy, the members' expected entropy,
+        their difference (the mutual information: how much of the uncertainty
+        is the members disagreeing), that on the wrongly against the other
+        examples, and the mean share of members off the vote — from one fused
+        sweep per batch over the members' logits (kernels.predict), the totals
+        staying on the device until one host read at the end.  The members are
+        `evaluate`'s: chains x collected components x nst draws (the same
+        Philox keys; `draws` advances as an `evaluate` over the loader would
+        advance it), uniformly weighted.  by_chain=True: every chain's own
+        mixture (the form for per_chain sweeps, cf. `evaluate_chains`), every
+        value a list of K.  per_example=True adds `per_example`: the [G, N]
+        tensors entropy, expected_entropy, mutual_info, confidence, nll, pred
+        and disagree, concatenated over the loader.  This process's chains only."""
+        from . import chains
+        if chains.world() > 1:
+            raise ValueError("uncertainty: the report describes this process's chains only, and "
+                             f"{chains.world()} processes share the predictive (run it in one "
+                             "process, or per process on its own chains before init)")
+        nb = int(num_bins if num_bins is not None else getattr(self.args, "ece_num_bins", None) or 15)
+        dev = self.args.device
+        G = self.K if by_chain else 1
+        want = K.PREDICT_DEFAULT_WANT if per_example else ()
+        tot, pieces, bufs = None, [], {}
+        was = self.net.training
+        self.net.eval()
+        try:
+            for x, y in loader:
+                x, y = x.to(dev), y.to(dev)
+                lg = self._member_logits(x, bufs)
+                outs, tot = K.predict(lg, y.to(torch.int64).contiguous(), groups=G, totals=tot,
+                                      num_bins=nb, want=want)
+                pieces.append(outs)
+        finally:
+            self.net.train(was)
+        if tot is None:
+            raise ValueError("uncertainty: the loader is empty")
+        rows = tot.summary()  # the one host read
+        res = {k: [r[k] for r in rows] for k in rows[0]} if by_chain else rows[0]
+        res["members"], res["num_bins"] = tot.members, nb
+        if per_example:
+            res["per_example"] = {w: torch.cat([p[w] for p in pieces], 1) for w in want}
+        return res
+
+    def _report_uncertainty(self, ep, rec, loader, log):
+        """One log line (one per chain under per_chain) and rec["uncertainty"]
+        from `uncertainty()` (run.py --uncertainty)."""
+        by_chain = self.per_chain is not None
+        try:
+            d = self.uncertainty(loader, by_chain=by_chain)
+        except ValueError as e:
+            log(f"(Epoch {ep}) uncertainty: {e}")
+            return
+        rec["uncertainty"] = d
+        for k in range(self.K if by_chain else 1):
+            r = {f: (v[k] if by_chain else v) for f, v in d.items() if f not in ("members",
+                                                                                   "num_bins")}
+            who = f"over {self.K} chains"
+            if by_chain:
+                who = f"chain {self.chain0 + k}: {PC.describe(self.per_chain, self.swept, k)}"
+            log(f"(Epoch {ep}) uncertainty {who} ({d['members']} members, {r['n']} examples): "
+                f"NLL = {r['nll']:.4f}, error = {r['error']:.4f}, ECE = {r['ece']:.4f}, "
+                f"MCE = {r['mce']:.4f} ({d['num_bins']} bins), entropy = {r['entropy']:.4f} "
+                f"(expected {r['expected_entropy']:.4f}), mutual information = "
+                f"{r['mutual_info']:.4f} (wrong {r['mutual_info_wrong']:.4f}, other "
+                f"{r['mutual_info_correct']:.4f}), disagreement = {r['disagreement']:.4f}; "
+                f"{r['n_nonfinite']} non-finite")
+
     # ---------------------------------------------------------- checkpoint
     def state_dict(self):
         """Everything an exact continuation of all K chains needs: the stacked
@@ -1067,6 +1162,8 @@ class _StackedSampler:
                 rec["test"] = self.evaluate(test_loader)
                 log(f"(Epoch {ep}) stacked predictive: loss = {rec['test'][0]:.4f}, "
                     f"error = {rec['test'][1]:.4f}")
+                if getattr(self.args, "uncertainty", False):  # opt-in (run.py --uncertainty)
+                    self._report_uncertainty(ep, rec, test_loader, log)
                 if self.per_chain is not None:
                     self._report_chains(ep, rec, test_loader, log)
                 if getattr(self.args, "rhat", False):  # opt-in (run.py --rhat)
