@@ -31,6 +31,17 @@
  * x * 1.0f is x bit for bit.  (norm_k, coef_k), k = 0 .. K-1, stand at the
  * start of the workspace as 2K floats.
  *
+ * Non-finite norms (part of the contract; bdl_sgld_step_clipped's one-chain
+ * finalize follows the same two rules):
+ *   NaN   a NaN among chain k's elements gives norm_k = NaN and, by fminf,
+ *         coef_k = 1: the chain is left exactly as it is.  This deviates from
+ *         torch.nn.utils.clip_grad_norm_, which multiplies every gradient of
+ *         that model by NaN; here the NaN stays where it was and the other
+ *         chains are clipped as usual.
+ *   +Inf  an infinite element, or a sum of squares whose root exceeds FLT_MAX,
+ *         gives norm_k = +Inf and coef_k = 0: finite elements become +-0 with
+ *         their sign, infinite ones NaN (as torch).
+ *
  * The sum is reduced without atomics: per-lane fp64 accumulators, a 64-lane
  * butterfly, the workgroup's waves through LDS, one partial per workgroup,
  * and per chain one workgroup that combines that chain's partials in a fixed

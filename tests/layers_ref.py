@@ -70,6 +70,12 @@ def split(offset, numel):
     return h, nbody, numel - h - 4 * nbody
 
 
+def rotated(w, i, grid):
+    """Workgroup w's index b in segment i's rotation (bdl_chain_common.hpp
+    rotated_block): b = 0 starts the segment and owns its head and tail."""
+    return (w + grid - i % grid) % grid
+
+
 def classify(segments, n, grid):
     """{(workgroup, segment): dict(part, iters, head, body, tail)} of one
     sweep: whether the workgroup takes part in the segment (else it stores an
@@ -83,7 +89,7 @@ def classify(segments, n, grid):
         assert m >= 1 and o >= 0 and o + m <= n
         h, nbody, tail = split(o, m)
         for w in range(grid):
-            b = (w - i) % grid
+            b = rotated(w, i, grid)
             starts = range(b * K_BLOCK, nbody, grid * K_BLOCK)
             part = b == 0 or b * K_BLOCK < nbody
             assert part or len(starts) == 0

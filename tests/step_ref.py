@@ -216,10 +216,15 @@ def sgld(th, th0, g, buf, attr, sc, eps, mode, momentum=None, clip_coef=None):
 
 def clip_coef(norm, max_norm):
     """clip_grad_norm_'s coefficient from a total norm: max_norm / (norm + 1e-6)
-    as reciprocal() * max_norm, clamped at 1."""
-    r = F(1.0) / (F(norm) + F(1e-6))
-    c = r * f32(max_norm)
-    return min(c, F(1.0))
+    as reciprocal() * max_norm, clamped at 1 with fminf.  A NaN norm gives 1
+    (fminf returns its other operand): the gradient is left as it is, where
+    clip_grad_norm_ would multiply it by NaN (include/bdl_clip.h)."""
+    with np.errstate(all="ignore"):
+        r = F(1.0) / (F(norm) + F(1e-6))
+        c = F(r * f32(max_norm))
+    if np.isnan(c):
+        return F(1.0)
+    return c if c < F(1.0) else F(1.0)
 
 
 # ---------------------------------------------------------------------- SGHMC
