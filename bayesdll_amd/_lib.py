@@ -358,6 +358,24 @@ PREDICT_EXPORTS = {
     "bdl_predict": (C.c_int, [C.POINTER(PredictArgs), C.c_void_p]),
 }
 
+
+class FnFoldArgs(C.Structure):
+    """include/bdl_fn.h bdl_fn_fold_args."""
+    _fields_ = [("logits", _fp), ("bsum", _fp), ("smean", _fp), ("sM2", _fp), ("bM2", _fp),
+                ("probs", _fp), ("probe", C.c_int64), ("chain_groups", C.c_uint64),
+                ("sample", C.c_int64), ("batch", C.c_int64), ("chains", C.c_int32),
+                ("classes", C.c_int32), ("flags", C.c_int32), ("fs", C.c_float),
+                ("fb", C.c_float), ("c", C.c_float), ("grid_blocks", C.c_int32),
+                ("pad0", C.c_int32)]
+
+
+FN_MAX_CLASSES, FN_WAVE_CLASSES, FN_MAX_GRID = 8192, 256, 2048
+
+# include/bdl_fn.h: additive to the ABI, as DIAG_EXPORTS
+FN_EXPORTS = {
+    "bdl_fn_fold": (C.c_int, [C.POINTER(FnFoldArgs), C.c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -382,7 +400,8 @@ def lib():
                                       + list(ESS_EXPORTS.items())
                                       + list(LOWP_EXPORTS.items())
                                       + list(LAYERS_EXPORTS.items())
-                                      + list(PREDICT_EXPORTS.items())):
+                                      + list(PREDICT_EXPORTS.items())
+                                      + list(FN_EXPORTS.items())):
                 fn = getattr(h, name)
                 fn.restype = res
                 fn.argtypes = argt

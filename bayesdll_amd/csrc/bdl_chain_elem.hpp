@@ -2,7 +2,8 @@
 // (include/bdl_diag.h, include/bdl_ess.h) and the adapters between their public
 // summary structs and Extreme.  bdl_diag.hip / bdl_ess.hip (the whole-vector
 // sweeps) and bdl_layers.hip (the per-tensor tables) instantiate these ONE
-// definitions, so an element's value cannot differ between them.
+// definitions, so an element's value cannot differ between them; so do the two
+// folds (bdl_ess.hip of theta, bdl_fn.hip of the probe probabilities).
 //
 // A: the unit's own kernel-argument struct.  The diagnostic reads ratio,
 // inv_ratio, var_floor, c1, fk, fkm1 (K and K - 1 as fp32) and thr0..2 of it;
@@ -127,6 +128,45 @@ __device__ __forceinline__ void diag_finish_elem(const A& a, float m0, float S1,
 }
 
 // --------------------------------------------------------------------- ESS
+// One element of the batch-means fold (include/bdl_ess.h, one rounding per
+// line): the sample x into its Welford mean / M2, its open batch sum and, on a
+// CLOSE, the M2 of the batch means.  bdl_ess.hip folds theta with it,
+// bdl_fn.hip the probe probabilities.
+template <int FLAGS>
+__device__ __forceinline__ void ess_fold_elem(float x, float& sm, float& M, float& bs, float& B,
+                                              float fs, float fb, float c) {
+  constexpr bool kFirstSample = FLAGS & BDL_ESS_FIRST_SAMPLE;
+  constexpr bool kFirstInBatch = FLAGS & BDL_ESS_FIRST_IN_BATCH;
+  constexpr bool kClose = FLAGS & BDL_ESS_CLOSE;
+  constexpr bool kFirstBatch = FLAGS & BDL_ESS_FIRST_BATCH;
+  if constexpr (kFirstSample) {
+    sm = x;
+    M = 0.0f;
+  } else {
+    const float d = x - sm;
+    const float q = d / fs;
+    sm = sm + q;
+    const float d2 = x - sm;
+    const float t = d * d2;
+    M = M + t;
+  }
+  if constexpr (kFirstInBatch)
+    bs = x;
+  else
+    bs = bs + x;
+  if constexpr (kClose) {
+    if constexpr (kFirstBatch) {
+      B = 0.0f;
+    } else {
+      const float y = bs / fb;
+      const float ee = y - sm;
+      const float t = ee * ee;
+      const float u = t * c;
+      B = B + u;
+    }
+  }
+}
+
 __device__ __forceinline__ void ess_accum4(const f4v m, const f4v q, f4v& SW, f4v& SV) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) {

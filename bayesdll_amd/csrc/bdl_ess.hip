@@ -54,32 +54,12 @@ __device__ __forceinline__ void fold_group(const FArgs& a, int64_t o, int64_t gi
   if constexpr (kClose && !kFirstBatch) B = gload<GUARD>(a.bM2 + o, e, a.n);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    if constexpr (kFirstSample) {
-      sm[j] = x[j];
-      M[j] = 0.0f;
-    } else {
-      const float d = x[j] - sm[j];
-      const float q = d / a.fs;
-      sm[j] = sm[j] + q;
-      const float d2 = x[j] - sm[j];
-      const float t = d * d2;
-      M[j] = M[j] + t;
-    }
-    if constexpr (kFirstInBatch)
-      bs[j] = x[j];
-    else
-      bs[j] = bs[j] + x[j];
-    if constexpr (kClose) {
-      if constexpr (kFirstBatch) {
-        B[j] = 0.0f;
-      } else {
-        const float y = bs[j] / a.fb;
-        const float ee = y - sm[j];
-        const float t = ee * ee;
-        const float u = t * a.c;
-        B[j] = B[j] + u;
-      }
-    }
+    float s1 = sm[j], m2 = M[j], b1 = bs[j], b2 = B[j];
+    ess_fold_elem<FLAGS>(x[j], s1, m2, b1, b2, a.fs, a.fb, a.c);
+    sm[j] = s1;
+    M[j] = m2;
+    bs[j] = b1;
+    B[j] = b2;
   }
   gstore<GUARD>(a.smean + o, e, a.n, sm);
   gstore<GUARD>(a.sM2 + o, e, a.n, M);

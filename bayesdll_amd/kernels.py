@@ -625,6 +625,58 @@ def ess_fold(theta, bsum, smean, sM2, bM2, *, chains, chain_groups, n, sample, b
     return flags
 
 
+def fn_fold(logits, bsum, smean, sM2, bM2, *, sample, batch, chain_groups, probs=None,
+            grid_blocks=0):
+    """Fold the class probabilities of every chain on a probe batch into the
+    batch-means accumulators (bdl_fn_fold, include/bdl_fn.h): logits is the
+    contiguous fp32 [chains, probe, classes] of one collected sample, softmax
+    and fold are one sweep with no probability tensor in between.  The
+    accumulators are stacked as ess_fold's (chain k, element b*classes + c at
+    4*chain_groups*k + b*classes + c); `sample`, `batch`, flags and scalars as
+    there; bsum may be None at b == 1.  probs: an optional [chains, probe,
+    classes] fp32 tensor that receives the folded probabilities.  One launch on
+    the current stream, no host synchronisation.  Values never depend on
+    grid_blocks (workgroups, 0: default).  Returns the flags."""
+    flags, fs, fb, c = E.fold_plan(sample, batch)
+    if not torch.is_tensor(logits) or logits.dim() != 3:
+        raise ValueError("fn_fold: logits must be a [chains, probe, classes] tensor")
+    L.require_hip(logits, "logits")
+    if not logits.is_contiguous():
+        raise ValueError("fn_fold: logits must be contiguous")
+    chains, probe, classes = (int(v) for v in logits.shape)
+    if probe < 1:
+        raise ValueError("fn_fold: the probe batch is empty")
+    if not 1 <= classes <= L.FN_MAX_CLASSES:
+        raise ValueError(f"fn_fold: 1 <= classes <= {L.FN_MAX_CLASSES} is required")
+    if not 0 <= int(grid_blocks) <= L.FN_MAX_GRID:
+        raise ValueError(f"fn_fold: grid_blocks in [0, {L.FN_MAX_GRID}]")
+    vecs = [("smean", smean), ("sM2", sM2), ("bM2", bM2)]
+    if int(batch) > 1:
+        if bsum is None:
+            raise ValueError("fn_fold: bsum is required with batch > 1")
+        vecs.append(("bsum", bsum))
+    chains, chain_groups, n, dev = _stacked_layout("fn_fold", vecs, chains, chain_groups,
+                                                   probe * classes)
+    if logits.device != dev:
+        raise ValueError("fn_fold: all vectors must be on one device")
+    if probs is not None:
+        L.require_hip(probs, "probs")
+        if not probs.is_contiguous() or probs.shape != logits.shape or probs.device != dev:
+            raise ValueError("fn_fold: probs must be a contiguous tensor of the logits' shape on "
+                             "their device")
+    a = L.FnFoldArgs()
+    a.logits = logits.data_ptr()
+    a.smean, a.sM2, a.bM2 = (t.data_ptr() for t in (smean, sM2, bM2))
+    a.bsum = bsum.data_ptr() if int(batch) > 1 else None
+    a.probs = None if probs is None else probs.data_ptr()
+    a.probe, a.chain_groups, a.chains, a.classes = probe, chain_groups, chains, classes
+    a.sample, a.batch, a.flags = int(sample), int(batch), flags
+    a.fs, a.fb, a.c = fs, fb, c
+    a.grid_blocks = int(grid_blocks)
+    L.check(L.lib().bdl_fn_fold(a, L.current_stream_handle(dev)), "bdl_fn_fold")
+    return flags
+
+
 def chain_ess_workspace(device):
     """The report's device scratch (summary + per-workgroup partials), one per device."""
     return _byte_scratch("ess", torch.device(device),

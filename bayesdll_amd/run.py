@@ -143,7 +143,45 @@ def build_parser():
                          "entropy, mutual information (overall, on wrong against other examples) "
                          "and member disagreement from one fused sweep over the members' logits "
                          "(stacked uncertainty()); per chain with --sweep")
+    ap.add_argument("--fn_probe", type=int, default=0, metavar="P",
+                    help="with --stacked_chains >= 1: fold the chains' class probabilities on "
+                         "the first P test examples into batch-means accumulators at every "
+                         "collect step (batches of --fn_batch samples) and log the function-space "
+                         "R-hat and effective sample size at every evaluation (stacked "
+                         "function_space()); ESS per chain with --sweep")
+    ap.add_argument("--fn_batch", type=int, default=0, metavar="B",
+                    help="with --fn_probe: the batch length of its batch-means accumulators "
+                         "(>= 1; several autocorrelation times long)")
     return ap
+
+
+def check_fn(ap, args):
+    """--fn_probe P needs stacked chains and --fn_batch B >= 1; --fn_batch
+    needs --fn_probe (ap.error otherwise)."""
+    if args.fn_probe < 0 or args.fn_batch < 0:
+        ap.error("--fn_probe / --fn_batch: P and B must be >= 0")
+    if args.fn_probe and args.stacked_chains < 1:
+        ap.error("--fn_probe folds the stacked chains' probe predictions: it needs "
+                 "--stacked_chains >= 1")
+    if args.fn_probe and args.fn_batch < 1:
+        ap.error("--fn_probe needs --fn_batch B >= 1 (the batch length of its accumulators)")
+    if args.fn_batch and not args.fn_probe:
+        ap.error("--fn_batch is the batch length of --fn_probe's accumulators: it needs "
+                 "--fn_probe P")
+    return args.fn_probe, args.fn_batch
+
+
+def first_examples(loader, n):
+    """The first n inputs of a loader, as one batch."""
+    xs, have = [], 0
+    for x, _ in loader:
+        xs.append(x)
+        have += len(x)
+        if have >= n:
+            break
+    if have < n:
+        raise ValueError(f"--fn_probe {n}: the test split holds only {have} examples")
+    return torch.cat(xs)[:n]
 
 
 def check_uncertainty(ap, args):
@@ -277,6 +315,7 @@ def main(argv=None):
     check_ess(ap, args)
     check_uncertainty(ap, args)
     check_by_tensor(ap, args)
+    check_fn(ap, args)
     check_compute_dtype(ap, args)
     from . import chains
     rank, world, device = chains.init_chains()
@@ -344,6 +383,9 @@ def main(argv=None):
             kw["health_every"] = args.health
         if args.ess:
             kw["ess_batch"] = args.ess
+        if args.fn_probe:
+            kw["fn_probe"] = first_examples(test_loader, args.fn_probe)
+            kw["fn_batch"] = args.fn_batch
         S = cls(net, args.stacked_chains, args, logger=logger, init="reinit", graph=args.graph,
                 net0=net0, **kw)
         logger.info(f"{args.stacked_chains} stacked chains on this device "

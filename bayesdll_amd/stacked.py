@@ -385,7 +385,7 @@ class _StackedSampler:
 
     def __init__(self, net, K_, args, *, chain0=None, seed=None, init="copy", criterion=None,
                  per_chain_batches=False, logger=None, graph=None, net0=None, per_chain=None,
-                 health_every=0, ess_batch=0):
+                 health_every=0, ess_batch=0, fn_probe=None, fn_batch=0):
         from . import chains
         from ._base import default_compute_dtype, default_graph, refuse_compute_dtype
         refuse_compute_dtype(getattr(args, "compute_dtype", None) or default_compute_dtype(),
@@ -398,6 +398,21 @@ class _StackedSampler:
         # unchanged and nothing is allocated)
         self.ess_batch = ESS.check_batch(ess_batch)
         self._ess = None  # [{bsum, smean, sM2, bM2}, samples folded into the latest component]
+        # function-space convergence: after `update` of every collect step the
+        # chains' class probabilities on the probe batch fn_probe [P, ...] are
+        # folded into batch-means accumulators of batch length fn_batch (None:
+        # never; then step() is unchanged and nothing is allocated)
+        self.fn_batch = ESS.check_batch(fn_batch, "fn_batch")
+        if fn_probe is None:
+            if self.fn_batch:
+                raise ValueError(f"fn_batch = {self.fn_batch} needs a probe batch (fn_probe)")
+        else:
+            if not torch.is_tensor(fn_probe) or fn_probe.dim() < 1 or fn_probe.shape[0] < 1:
+                raise ValueError("fn_probe must be a non-empty input batch [P, ...]")
+            if self.fn_batch < 1:
+                raise ValueError("fn_probe needs fn_batch = b >= 1, the batch length of the "
+                                 f"batch-means accumulators (got {fn_batch!r})")
+        self._fn = None  # {acc: {bsum, smean, sM2, bM2}, samples, chain_groups, probe, classes}
         # every m-th step the statistics sweep runs between gradients() and
         # update() (0: never; then step() is unchanged and nothing is allocated)
         self.health_every = int(health_every)
@@ -410,6 +425,7 @@ class _StackedSampler:
         self._graphs = {}
         hp = args.hparams
         self.net = net.to(args.device)
+        self._fn_probe = None if fn_probe is None else fn_probe.detach().to(args.device)
         self.prior_sig = float(hp["prior_sig"])
         self.Ninflate, self.nd = float(hp["Ninflate"]), float(hp["nd"])
         self.thin, self.nst = int(hp["thin"]), int(hp["nst"])
@@ -514,6 +530,8 @@ class _StackedSampler:
         self.update(grads, *a, **kw)
         if self.ess_batch and kw.get("collect") is not None:
             self._ess_fold(kw["collect"][0])
+        if self._fn_probe is not None and kw.get("collect") is not None:
+            self._fn_fold()
         return loss, out
 
     # ------------------------------------------------------------------ ess
@@ -622,6 +640,146 @@ class _StackedSampler:
                 f"{r['n_nonfinite']} non-finite")
             self._log_tensors(ep, log, f"ESS {who}", r, "ess_min", "ess_mean", "share_below",
                               "<", ".1f", worst=min)
+
+    # ------------------------------------------------------- function space
+    def _fn_fold(self):
+        """Fold the chains' class probabilities on the probe batch, at the
+        theta this step's collect just accumulated, into the function-space
+        accumulators: one no-grad forward of the K chains and one launch
+        (kernels.fn_fold), no host sync.  The counters run over the whole run:
+        predictions, unlike the per-cycle Gaussians, are comparable across
+        components."""
+        lg = self.chain_logits(self._fn_probe)
+        if lg.dim() != 3:
+            raise ValueError("fn_probe: the network must map the probe batch to [P, classes] "
+                             f"logits (got {tuple(lg.shape[1:])} per chain)")
+        lg = lg.float().contiguous()
+        f = self._fn
+        if f is None:
+            _, P, Cn = (int(v) for v in lg.shape)
+            cg = (P * Cn + 3) // 4
+            names = K.ESS_VECTORS if self.fn_batch > 1 else K.ESS_VECTORS[1:]
+            acc = {nm: torch.zeros(self.K * 4 * cg, dtype=torch.float32, device=lg.device)
+                   for nm in names}
+            f = self._fn = {"acc": acc, "samples": 0, "chain_groups": cg, "probe": P,
+                            "classes": Cn}
+        v = f["acc"]
+        K.fn_fold(lg, v.get("bsum"), v["smean"], v["sM2"], v["bM2"], sample=f["samples"] + 1,
+                  batch=self.fn_batch, chain_groups=f["chain_groups"])
+        f["samples"] += 1
+
+    def function_space_reset(self):
+        """Empty the function-space accumulators: the next fold is a first sample."""
+        if self._fn is not None:
+            self._fn["samples"] = 0
+
+    def function_space(self, *, rhat=False, ess=False, mcse=False, by_chain=False,
+                       thresholds=None, rhat_thresholds=None):
+        """Have the chains converged where it matters, in their predictions?
+        R-hat across the K chains and the batch-means effective sample size
+        within them of softmax(f(x_b; theta_t))[c] on the probe batch, per
+        (example, class), over every sample collected since the sampler was
+        built (or `function_space_reset`), from accumulators a fused sweep
+        folds the probe probabilities into at every collect step
+        (kernels.fn_fold, include/bdl_fn.h).  Chains that sit in permutation-
+        or sign-equivalent modes disagree in every parameter and agree here.
+
+        Returns {"rhat": `diagnostics()`'s summary fields (count = samples,
+        argmax_at = (example, class) of argmax), "ess": `ess()`'s summary
+        fields (argmin_at likewise), samples, batches, batch, probe, classes}.
+        rhat / ess / mcse=True add the [P, C] tensors of those names to the
+        part they belong to.  R-hat needs K >= 2 and 2 folded samples, ESS 2
+        closed batches; with K = 1 only the "ess" part is returned.
+        by_chain=True: "ess" is a list of K results, chain k's from its own
+        accumulators alone — the only form under per_chain hyperparameters,
+        whose chains target different posteriors, where R-hat is refused.  The
+        accumulators are no part of state_dict / checkpoints and restart empty
+        after load_ckpt.  This process's chains only."""
+        from . import chains
+        if self._fn_probe is None:
+            raise ValueError("function_space: this sampler was built without fn_probe")
+        if chains.world() > 1:
+            raise ValueError("function_space: the report describes this process's chains only, "
+                             f"and {chains.world()} processes run chains (run it in one process)")
+        if self.per_chain is not None:
+            if rhat:
+                raise ValueError("function_space: this sampler runs per_chain hyperparameters; "
+                                 "R-hat compares chains that target ONE posterior, and these "
+                                 "chains target different ones")
+            if not by_chain:
+                raise ValueError("function_space: this sampler runs per_chain hyperparameters; "
+                                 "the pooled report pools chains that target ONE posterior, and "
+                                 "these chains target different ones (ask for by_chain=True)")
+        if rhat and self.K < 2:
+            raise ValueError("function_space: R-hat compares chains; this sampler runs K = 1")
+        thr = ESS.thresholds(thresholds)
+        rthr = (1.01, 1.05, 1.1) if rhat_thresholds is None else tuple(
+            float(t) for t in rhat_thresholds)
+        if len(rthr) != 3:
+            raise ValueError(f"function_space: three R-hat thresholds (got {rthr!r})")
+        f = self._fn
+        try:
+            S_, nb = ESS.check_report(0 if f is None else f["samples"], self.fn_batch)
+        except ValueError as e:
+            raise ValueError(f"function_space: {e}") from None
+        v, cg, P, Cn = f["acc"], f["chain_groups"], f["probe"], f["classes"]
+        n, slot = P * Cn, 4 * cg
+        at = lambda i: (i // Cn, i % Cn) if i >= 0 else None  # noqa: E731
+        out = {"samples": S_, "batches": nb, "batch": self.fn_batch, "probe": P, "classes": Cn}
+        rres = None
+        if self.K >= 2 and self.per_chain is None:
+            # Welford moments of the true count, as `_moment_spec` hands them over
+            rres = K.chain_diag(v["smean"], v["sM2"], chains=self.K, chain_groups=cg, n=n,
+                                var_mode=L.VAR_WELFORD, ratio=float(S_ - 1), count=S_,
+                                thresholds=rthr, want=("rhat",) if rhat else ())
+        want = (("ess",) if ess else ()) + (("mcse",) if mcse else ())
+        launched = [K.chain_ess(v["sM2"][sl:], v["bM2"][sl:], chains=k, chain_groups=cg, n=n,
+                                samples=S_, batches=nb, thresholds=thr, want=want)
+                    for sl, k in ([(j * slot, 1) for j in range(self.K)] if by_chain
+                                  else [(0, self.K)])]
+        if rres is not None:
+            r = dict(rres.summary)
+            r["count"], r["argmax_at"] = S_, at(r["argmax"])
+            if rhat:
+                r["rhat"] = rres["rhat"].view(P, Cn)
+            out["rhat"] = r
+        parts = []
+        for res in launched:
+            e = ESS.summary_dict(res.summary, thr, samples=S_, batches=nb, batch=self.fn_batch,
+                                 chains=self.K if not by_chain else 1)
+            e["argmin_at"] = at(e["argmin"])
+            e.update({w: res[w].view(P, Cn) for w in want})
+            parts.append(e)
+        out["ess"] = parts if by_chain else parts[0]
+        return out
+
+    def _report_function_space(self, ep, rec, log):
+        """One log line and rec["function_space"] from `function_space()`
+        (run.py --fn_probe); an evaluation that comes before the counts suffice
+        says so and goes on."""
+        by_chain = self.per_chain is not None
+        try:
+            d = self.function_space(by_chain=by_chain)
+        except ValueError as e:
+            log(f"(Epoch {ep}) {e}")
+            return
+        rec["function_space"] = d
+        es = d["ess"] if by_chain else [d["ess"]]
+        msg = (f"(Epoch {ep}) function space over {self.K} chains, {d['probe']} probe examples x "
+               f"{d['classes']} classes ({d['samples']} samples each, {d['batches']} batches of "
+               f"{d['batch']})")
+        if "rhat" in d:
+            r = d["rhat"]
+            msg += (f": R-hat max = {r['rhat_max']:.4f} at {r['argmax_at']}, mean = "
+                    f"{r['rhat_mean']:.4f}, > {r['thresholds'][0]:g}: "
+                    f"{100 * r['share_above'][0]:.1f} %")
+        msg += ("; ESS min = " + ", ".join(f"{e['ess_min']:.1f} at {e['argmin_at']}" for e in es)
+                + ", mean = " + ", ".join(f"{e['ess_mean']:.1f}" for e in es)
+                + f", < {es[0]['thresholds'][0]:g}: "
+                + ", ".join(f"{100 * e['share_below'][0]:.1f} %" for e in es)
+                + f"; {sum(e['n_degenerate'] for e in es)} degenerate, "
+                + f"{sum(e['n_nonfinite'] for e in es)} non-finite")
+        log(msg)
 
     def _by_tensor(self):
         """How many tensors the reports list (run.py --by_tensor N; 0: none)."""
@@ -1133,6 +1291,7 @@ class _StackedSampler:
             self._health[2] = 0
         if self._ess is not None:     # nor are these: the next fold is a first sample
             self._ess[1] = 0
+        self.function_space_reset()   # nor the function-space ones
         return d
 
     def train(self, train_loader, test_loader=None, start_epoch=0):
@@ -1170,6 +1329,8 @@ class _StackedSampler:
                     self._report_rhat(ep, rec, log)
                 if self.ess_batch:  # opt-in (run.py --ess)
                     self._report_ess(ep, rec, log)
+                if self._fn_probe is not None:  # opt-in (run.py --fn_probe)
+                    self._report_function_space(ep, rec, log)
             if self.health_every:  # opt-in (run.py --health)
                 self._report_health(ep, rec, log)
             hist.append(rec)
