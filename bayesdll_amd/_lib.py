@@ -376,6 +376,55 @@ FN_EXPORTS = {
     "bdl_fn_fold": (C.c_int, [C.POINTER(FnFoldArgs), C.c_void_p]),
 }
 
+TEMPER_MAX_CLASSES, TEMPER_WAVE_CLASSES, TEMPER_MAX_BINS = 8192, 256, 64
+TEMPER_MAX_GROUPS, TEMPER_MAX_GRID, TEMPER_MAX_ITER = 65535, 1024, 1024
+TEMPER_MAX_T, TEMPER_MIN_T = 100.0, 0.01
+TEMPER_RESET = 0x1
+
+
+class TemperState(C.Structure):
+    """include/bdl_temper.h bdl_temper_state (one per group, device memory)."""
+    _fields_ = [("nll", C.c_double), ("nll_first", C.c_double), ("d1", C.c_double),
+                ("d2", C.c_double), ("n", C.c_int64), ("n_nonfinite", C.c_int64),
+                ("n_inf_label", C.c_int64), ("beta", C.c_float), ("iterations", C.c_int32),
+                ("sweeps", C.c_int32), ("converged", C.c_int32), ("at_bound", C.c_int32),
+                ("degenerate", C.c_int32), ("done", C.c_int32), ("pad0", C.c_int32)]
+
+
+class TemperFitArgs(C.Structure):
+    """include/bdl_temper.h bdl_temper_fit_args."""
+    _fields_ = [("logp", _fp), ("labels", _fp), ("state", _fp), ("workspace", _fp),
+                ("batch", C.c_int64), ("rtol", C.c_double), ("groups", C.c_int32),
+                ("classes", C.c_int32), ("grid_blocks", C.c_int32), ("max_iter", C.c_int32)]
+
+
+class TemperTotals(C.Structure):
+    """include/bdl_temper.h bdl_temper_totals (one per group, device memory)."""
+    _fields_ = [("n", C.c_int64), ("n_labelled", C.c_int64), ("n_nonfinite", C.c_int64),
+                ("n_wrong", C.c_int64), ("nll_sum", C.c_double), ("entropy_sum", C.c_double),
+                ("confidence_sum", C.c_double),
+                ("bin_count", C.c_int64 * TEMPER_MAX_BINS),
+                ("bin_hits", C.c_int64 * TEMPER_MAX_BINS),
+                ("bin_conf", C.c_double * TEMPER_MAX_BINS)]
+
+
+class TemperReportArgs(C.Structure):
+    """include/bdl_temper.h bdl_temper_report_args."""
+    _fields_ = [("logp", _fp), ("labels", _fp), ("state", _fp), ("totals", _fp),
+                ("workspace", _fp), ("batch", C.c_int64), ("groups", C.c_int32),
+                ("classes", C.c_int32), ("num_bins", C.c_int32), ("grid_blocks", C.c_int32),
+                ("flags", C.c_int32), ("pad0", C.c_int32),
+                ("edges", C.c_float * TEMPER_MAX_BINS)]
+
+
+# include/bdl_temper.h: additive to the ABI, as DIAG_EXPORTS
+TEMPER_EXPORTS = {
+    "bdl_temper_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "bdl_temper_fit_sweep": (C.c_int, [C.POINTER(TemperFitArgs), C.c_void_p]),
+    "bdl_temper_fit_update": (C.c_int, [C.POINTER(TemperFitArgs), C.c_void_p]),
+    "bdl_temper_report": (C.c_int, [C.POINTER(TemperReportArgs), C.c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -401,7 +450,8 @@ def lib():
                                       + list(LOWP_EXPORTS.items())
                                       + list(LAYERS_EXPORTS.items())
                                       + list(PREDICT_EXPORTS.items())
-                                      + list(FN_EXPORTS.items())):
+                                      + list(FN_EXPORTS.items())
+                                      + list(TEMPER_EXPORTS.items())):
                 fn = getattr(h, name)
                 fn.restype = res
                 fn.argtypes = argt

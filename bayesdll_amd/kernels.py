@@ -978,6 +978,190 @@ def predict(logits, labels=None, *, groups=1, totals=None, reset=False, num_bins
     return outs, totals
 
 
+def _temper_rows(what, logp, labels, groups, grid_blocks):
+    """The checks `temper_fit` and `temper_report` share, worded as predict's;
+    returns (G, N, C, grid, workspace)."""
+    if not torch.is_tensor(logp) or logp.dim() < 2:
+        raise ValueError(f"{what}: logp must be a [G, N, C] tensor")
+    L.require_hip(logp, "logp")
+    if not logp.is_contiguous():
+        raise ValueError(f"{what}: logp must be contiguous")
+    G = int(groups)
+    N, Cn = int(logp.shape[-2]), int(logp.shape[-1])
+    lead = logp.numel() // max(N * Cn, 1)
+    if not 1 <= G <= L.TEMPER_MAX_GROUPS or N < 1 or lead != G:
+        raise ValueError(f"{what}: {tuple(logp.shape)} is not groups ({G}) x N x C")
+    if not 1 <= Cn <= L.TEMPER_MAX_CLASSES:
+        raise ValueError(f"{what}: 1 <= classes <= {L.TEMPER_MAX_CLASSES} (got {Cn})")
+    grid = int(grid_blocks)
+    if not 0 <= grid <= L.TEMPER_MAX_GRID:
+        raise ValueError(f"{what}: grid_blocks in [0, {L.TEMPER_MAX_GRID}]")
+    dev = logp.device
+    if labels is not None:
+        if (not torch.is_tensor(labels) or labels.dtype != torch.int64 or labels.shape != (N,)
+                or not labels.is_contiguous() or labels.device != dev):
+            raise ValueError(f"{what}: labels must be a contiguous int64 [N] tensor on the logp's "
+                             "device")
+    if grid == 0:  # the library's default, so that the workspace is sized for it
+        per_group = -(-N // (4 if Cn <= L.TEMPER_WAVE_CLASSES else 1))
+        cus = torch.cuda.get_device_properties(dev).multi_processor_count
+        grid = max(1, min(min(per_group, L.TEMPER_MAX_GRID) * G, 4 * cus, L.TEMPER_MAX_GRID))
+    nbytes = int(L.lib().bdl_temper_workspace_bytes(G, grid))
+    ws = _scratch(("temper", dev.index, nbytes),
+                  lambda: torch.empty(nbytes, dtype=torch.uint8, device=dev))
+    return G, N, Cn, grid, ws
+
+
+def temper_betas(temperature, groups):
+    """[G] fp32 beta = 1 / T of a float or a length-G sequence of temperatures
+    in [TEMPER_MIN_T, TEMPER_MAX_T] (the value the kernels multiply by)."""
+    t = np.asarray(temperature, dtype=np.float64)
+    if t.ndim == 0:
+        t = np.full(int(groups), float(t))
+    if t.shape != (int(groups),):
+        raise ValueError(f"temper: temperature must be a float or {int(groups)} values, one per "
+                         "group")
+    if not (np.isfinite(t).all() and (t >= L.TEMPER_MIN_T).all() and (t <= L.TEMPER_MAX_T).all()):
+        raise ValueError(f"temper: {L.TEMPER_MIN_T} <= temperature <= {L.TEMPER_MAX_T}")
+    return (1.0 / t).astype(np.float32)
+
+
+class TemperState:
+    """bdl_temper_state[groups] in device memory: the per-group beta = 1 / T and
+    what the fit's last sweep found.  `read()` is the one host read (a
+    structured array with the struct's fields), `summary()` one dict per group,
+    `temperatures()` the [G] temperatures as a device tensor (no host read)."""
+
+    def __init__(self, betas, device):
+        host = np.zeros(len(betas), dtype=np.dtype(L.TemperState))
+        host["beta"] = betas
+        self.groups = len(betas)
+        self.buf = torch.from_numpy(host.view(np.uint8).copy()).to(device)
+
+    def read(self):
+        return np.frombuffer(self.buf.cpu().numpy().tobytes(), dtype=np.dtype(L.TemperState))
+
+    def betas(self):
+        """[G] fp32 view of the struct's beta fields (device memory)."""
+        words = self.buf.view(torch.float32).view(self.groups, -1)
+        return words[:, L.TemperState.beta.offset // 4]
+
+    def temperatures(self):
+        return 1.0 / self.betas()
+
+    def summary(self):
+        return [{"temperature": 1.0 / float(r["beta"]), "nll_before": float(r["nll_first"]),
+                 "nll_after": float(r["nll"]), "iterations": int(r["iterations"]),
+                 "converged": bool(r["converged"]), "at_bound": bool(r["at_bound"]),
+                 "degenerate": bool(r["degenerate"]), "n": int(r["n"]),
+                 "n_nonfinite": int(r["n_nonfinite"]), "n_inf_label": int(r["n_inf_label"])}
+                for r in self.read()]
+
+
+def temper_fit(logp, labels, groups=1, rtol=1e-6, max_iter=32, grid_blocks=0):
+    """One scalar temperature per group, fitted on the device to the
+    sample-averaged log-probabilities `logp` [G, N, C] (what predict's `logp`
+    output is) and int64 labels [N]: a safeguarded Newton iteration in
+    beta = 1 / T from T = 1 (include/bdl_temper.h: the definitions, the special
+    values, the update rule).  `max_iter` (sweep, update) pairs are enqueued
+    back to back on the current stream with no host read in between; the
+    TemperState handle returned reads the device once, in `.summary()`: per
+    group temperature, nll_before (at T = 1), nll_after, iterations, converged,
+    at_bound, degenerate, n, n_nonfinite, n_inf_label.  A group that is neither
+    converged nor degenerate did not converge (at_bound: its optimum is at or
+    beyond a limit of T, and it stopped sweeping once it sat there)."""
+    G, N, Cn, grid, ws = _temper_rows("temper_fit", logp, labels, groups, grid_blocks)
+    iters, rt = int(max_iter), float(rtol)
+    if not 1 <= iters <= L.TEMPER_MAX_ITER:
+        raise ValueError(f"temper_fit: 1 <= max_iter <= {L.TEMPER_MAX_ITER} (got {iters})")
+    if not 0.0 <= rt < 1.0:
+        raise ValueError(f"temper_fit: 0 <= rtol < 1 (got {rtol})")
+    dev = logp.device
+    state = TemperState(np.ones(G, dtype=np.float32), dev)
+    a = L.TemperFitArgs()
+    a.logp = logp.data_ptr()
+    a.labels = None if labels is None else labels.data_ptr()
+    a.state, a.workspace = state.buf.data_ptr(), ws.data_ptr()
+    a.batch, a.rtol, a.groups, a.classes, a.grid_blocks, a.max_iter = N, rt, G, Cn, grid, iters
+    h, st = L.lib(), L.current_stream_handle(dev)
+    for _ in range(iters):
+        L.check(h.bdl_temper_fit_sweep(a, st), "bdl_temper_fit_sweep")
+        L.check(h.bdl_temper_fit_update(a, st), "bdl_temper_fit_update")
+    return state
+
+
+def temper_summary(row, num_bins):
+    """One group's host-read bdl_temper_totals as a dict: n, nll, error, ece /
+    mce (calibration.analyze's formula on the bins), entropy, confidence, bins,
+    n_labelled, n_nonfinite.  A mean over nothing is NaN."""
+    full = predict_summary({**{k: row[k] for k in ("n", "n_labelled", "n_nonfinite", "n_wrong",
+                                                    "nll_sum", "entropy_sum", "bin_count",
+                                                    "bin_hits", "bin_conf")},
+                            "expected_entropy_sum": 0.0, "mi_sum": 0.0, "mi_sum_wrong": 0.0,
+                            "disagree_sum": 0}, 1, num_bins)
+    out = {k: full[k] for k in ("n", "n_labelled", "n_nonfinite", "nll", "error", "ece", "mce",
+                                "entropy", "bins")}
+    n = int(row["n"])
+    out["confidence"] = float(row["confidence_sum"]) / n if n else float("nan")
+    return out
+
+
+class TemperTotals:
+    """The running totals of `temper_report` calls: bdl_temper_totals[groups] in
+    device memory.  `read()` is the one host read, `summary()` the dict(s) of
+    temper_summary."""
+
+    def __init__(self, groups, num_bins, device):
+        self.groups, self.num_bins = int(groups), int(num_bins)
+        self.buf = torch.empty(self.groups * C.sizeof(L.TemperTotals), dtype=torch.uint8,
+                               device=device)
+        self.fresh = True  # nothing accumulated: the first call resets
+
+    def read(self):
+        if self.fresh:
+            raise ValueError("temper_report: these totals hold nothing yet")
+        return np.frombuffer(self.buf.cpu().numpy().tobytes(), dtype=np.dtype(L.TemperTotals))
+
+    def summary(self):
+        return [temper_summary(r, self.num_bins) for r in self.read()]
+
+
+def temper_report(logp, labels, temperature, groups=1, totals=None, num_bins=15, grid_blocks=0):
+    """NLL, error, ECE / MCE, entropy and confidence of q = softmax(logp / T)
+    per group (bdl_temper_report, include/bdl_temper.h), added to `totals` in
+    device memory (a new TemperTotals, or the one passed in).  temperature: a TemperState (a fitted temperature never
+    visits the host), a float, or a length-G sequence.  Two launches on the
+    current stream, no host read here: totals.read() / .summary() is the one."""
+    G, N, Cn, grid, ws = _temper_rows("temper_report", logp, labels, groups, grid_blocks)
+    nb = int(num_bins)
+    if not 1 <= nb <= L.TEMPER_MAX_BINS:
+        raise ValueError(f"temper_report: 1 <= num_bins <= {L.TEMPER_MAX_BINS} (got {nb})")
+    dev = logp.device
+    state = temperature
+    if not isinstance(state, TemperState):
+        state = TemperState(temper_betas(temperature, G), dev)
+    elif state.groups != G or state.buf.device != dev:
+        raise ValueError("temper_report: this state was fitted with other groups or on another "
+                         "device")
+    if totals is None:
+        totals = TemperTotals(G, nb, dev)
+    elif (totals.groups, totals.num_bins) != (G, nb) or totals.buf.device != dev:
+        raise ValueError("temper_report: these totals were started with other groups / num_bins "
+                         "or on another device")
+    a = L.TemperReportArgs()
+    a.logp = logp.data_ptr()
+    a.labels = None if labels is None else labels.data_ptr()
+    a.state, a.totals, a.workspace = state.buf.data_ptr(), totals.buf.data_ptr(), ws.data_ptr()
+    a.batch, a.groups, a.classes, a.num_bins, a.grid_blocks = N, G, Cn, nb, grid
+    a.flags = L.TEMPER_RESET if totals.fresh else 0
+    for i, e in enumerate(predict_edges(nb)):
+        a.edges[i] = float(e)
+    L.check(L.lib().bdl_temper_report(a, L.current_stream_handle(dev)), "bdl_temper_report")
+    totals.fresh = False
+    totals.state = state  # keeps an uploaded temperature alive until the launches ran
+    return totals
+
+
 def clip_bytes_per_elem(clipped_share=1.0):
     """Algorithmic HBM bytes per gradient element of one chain_clip call
     (DESIGN §4e): every element read once for the norm; the elements of the

@@ -143,6 +143,13 @@ def build_parser():
                          "entropy, mutual information (overall, on wrong against other examples) "
                          "and member disagreement from one fused sweep over the members' logits "
                          "(stacked uncertainty()); per chain with --sweep")
+    ap.add_argument("--temperature_scale", action="store_true",
+                    help="with --stacked_chains >= 1 and --val_heldout > 0: after training, fit a "
+                         "scalar temperature to the stacked predictive on the validation split "
+                         "on the device (stacked fit_temperature()) and log the test split's "
+                         "ECE / MCE / NLL at T = 1 and at the fitted temperature (what the "
+                         "one-chain Runners' calibration block reports, under this path's "
+                         "own line for T = 1); per chain with --sweep")
     ap.add_argument("--fn_probe", type=int, default=0, metavar="P",
                     help="with --stacked_chains >= 1: fold the chains' class probabilities on "
                          "the first P test examples into batch-means accumulators at every "
@@ -190,6 +197,44 @@ def check_uncertainty(ap, args):
         ap.error("--uncertainty reports the stacked chains' predictive: it needs "
                  "--stacked_chains >= 1")
     return args.uncertainty
+
+
+def check_temperature_scale(ap, args):
+    """--temperature_scale needs stacked chains and a validation split
+    (ap.error otherwise)."""
+    if args.temperature_scale and args.stacked_chains < 1:
+        ap.error("--temperature_scale fits the stacked chains' predictive: it needs "
+                 "--stacked_chains >= 1")
+    if args.temperature_scale and not args.val_heldout > 0:
+        ap.error("--temperature_scale fits the temperature on the validation split: it needs "
+                 "--val_heldout > 0")
+    return args.temperature_scale
+
+
+def report_temperature_scale(S, val_loader, test_loader, rec, log):
+    """What the reference Runners' calibration block reports, for the stacked
+    predictive: the test split's ECE / MCE / NLL at T = 1 (this path's own
+    line, `[Calibration - No temp scaling]`; the Runners print `[Calibration -
+    Default T=1]`), then at the temperature fitted on the validation split
+    (the reference's `Temp-scaled` line, or its failure line), one pair per
+    chain under a per_chain sweep, and both in rec["calibration"]."""
+    by_chain = S.per_chain is not None
+    fit = S.fit_temperature(val_loader, by_chain=by_chain)
+    d = S.uncertainty(test_loader, by_chain=by_chain, temperature="fitted")
+    rec["calibration"] = {"fit": fit, "T1": {k: d[k] for k in ("ece", "mce", "nll")},
+                          "Topt": d["scaled"]}
+    for k in range(S.K if by_chain else 1):
+        f, r, s = ({key: (v[k] if by_chain else v) for key, v in m.items()}
+                   for m in (fit, rec["calibration"]["T1"], d["scaled"]))
+        who = f" chain {S.chain0 + k}" if by_chain else ""
+        log(f"[Calibration - No temp scaling]{who} ECE = {r['ece']:.4f}, MCE = {r['mce']:.4f}, "
+            f"NLL = {r['nll']:.4f}")
+        if f["converged"]:
+            log(f"[Calibration - Temp-scaled Topt={s['temperature']:.4f}]{who} ECE = "
+                f"{s['ece']:.4f}, MCE = {s['mce']:.4f}, NLL = {s['nll']:.4f}")
+        else:
+            log(f"!! Temperature scaling optimization failed !!{who}")
+    return rec["calibration"]
 
 
 def check_by_tensor(ap, args):
@@ -314,6 +359,7 @@ def main(argv=None):
     check_health(ap, args)
     check_ess(ap, args)
     check_uncertainty(ap, args)
+    check_temperature_scale(ap, args)
     check_by_tensor(ap, args)
     check_fn(ap, args)
     check_compute_dtype(ap, args)
@@ -345,6 +391,9 @@ def main(argv=None):
     logger.info(f"Command :: {' '.join(sys.argv)}  (chain {rank} of {world})\n")
 
     train_loader, val_loader, test_loader, args.ND = prepare(args, device)
+    if args.temperature_scale and val_loader is None:  # before any training is spent
+        raise ValueError("--temperature_scale: the validation split is empty "
+                         "(--val_heldout x the training set rounds to 0)")
     from .backbones import create_backbone
     net = create_backbone(args)
     logger.info("Total params in the backbone: %.2fM"
@@ -391,6 +440,10 @@ def main(argv=None):
         logger.info(f"{args.stacked_chains} stacked chains on this device "
                     f"(chain ids {S.chain0}..{S.chain0 + S.K - 1})")
         hist = S.train(train_loader, test_loader)
+        if args.temperature_scale:
+            if not hist:  # --epochs 0: the chains as initialised
+                hist.append({})
+            report_temperature_scale(S, val_loader, test_loader, hist[-1], logger.info)
         if sweep is not None:
             # rank the sweep on held-out data (the test split without one)
             from .per_chain import describe

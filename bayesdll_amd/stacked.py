@@ -348,6 +348,15 @@ def st_big(st):
     return st.device.type == "cuda" and st.n >= 1 << 20
 
 
+def _single_process(what):
+    """uncertainty / fit_temperature describe this process's chains only."""
+    from . import chains
+    if chains.world() > 1:
+        raise ValueError(f"{what}: the report describes this process's chains only, and "
+                         f"{chains.world()} processes share the predictive (run it in one "
+                         "process, or per process on its own chains before init)")
+
+
 class _StackedSampler:
     """What every stacked sampler shares: K chains' state, the vmapped
     forward/backward (optionally replayed from a HIP graph), the predictive
@@ -1178,7 +1187,68 @@ class _StackedSampler:
                 out[i].copy_(lg)
             return out
 
-    def uncertainty(self, loader, *, by_chain=False, num_bins=None, per_example=False):
+    temperature_ = None   # fit_temperature's [G] device tensor (not checkpointed)
+    _temper = None        # (by_chain, kernels.TemperState) of the last fit
+
+    def _loader_logp(self, loader, G):
+        """(logp [G, N, C], labels [N]) of `evaluate`'s members over the loader,
+        both on the device: predict's log mixture per batch, concatenated."""
+        dev = self.args.device
+        lps, ys, bufs = [], [], {}
+        was = self.net.training
+        self.net.eval()
+        try:
+            for x, y in loader:
+                x, y = x.to(dev), y.to(dev).to(torch.int64).contiguous()
+                outs, _ = K.predict(self._member_logits(x, bufs), y, groups=G, want=("logp",))
+                lps.append(outs["logp"])
+                ys.append(y)
+        finally:
+            self.net.train(was)
+        if not lps:
+            return None, None
+        return torch.cat(lps, 1).contiguous(), torch.cat(ys).contiguous()
+
+    def fit_temperature(self, loader, *, by_chain=False, rtol=1e-6, max_iter=32):
+        """Fit one scalar temperature (per chain with by_chain=True) to the
+        stacked predictive on a held-out loader, on the device: T minimises the
+        NLL of softmax(logp / T), logp the sample-averaged log-probabilities of
+        `evaluate`'s members (the same Philox keys and the same advance of
+        `draws` as `uncertainty`) — the reference's temperature scaling.  logp
+        [G, N, C] and the labels stay on the device, the Newton iteration
+        (kernels.temper_fit) runs there, and its state is read once.  Stores
+        `temperature_` ([G] device tensor) for `uncertainty(...,
+        temperature="fitted")` and returns the fit's summary (temperature,
+        nll_before, nll_after, iterations, converged, at_bound, degenerate, n,
+        n_nonfinite, n_inf_label; lists of K under by_chain).  Not part of
+        state_dict.  This process's chains only."""
+        _single_process("fit_temperature")
+        G = self.K if by_chain else 1
+        logp, y = self._loader_logp(loader, G)
+        if logp is None:
+            raise ValueError("fit_temperature: the loader is empty")
+        state = K.temper_fit(logp, y, groups=G, rtol=rtol, max_iter=max_iter)
+        rows = state.summary()  # the one host read
+        self._temper = (bool(by_chain), state)
+        self.temperature_ = state.temperatures()
+        return {k: [r[k] for r in rows] for k in rows[0]} if by_chain else rows[0]
+
+    def _temperature_state(self, temperature, by_chain, G):
+        """The kernels.TemperState `uncertainty` reports at."""
+        if isinstance(temperature, str):
+            if temperature != "fitted":
+                raise ValueError('uncertainty: temperature is a float, a sequence or "fitted"')
+            if self._temper is None:
+                raise ValueError('uncertainty: temperature="fitted" needs a fit_temperature() '
+                                 "first")
+            if self._temper[0] != bool(by_chain):
+                raise ValueError(f"uncertainty: the temperature was fitted with by_chain="
+                                 f"{self._temper[0]}, not by_chain={bool(by_chain)} (fit it again)")
+            return self._temper[1]
+        return K.TemperState(K.temper_betas(temperature, G), self.args.device)
+
+    def uncertainty(self, loader, *, by_chain=False, num_bins=None, per_example=False,
+                    temperature=None):
         """What the ensemble is for, over a data loader (the network in eval
         mode, as `evaluate`): NLL, error, ECE / MCE over `num_bins` confidence
         bins of every (example, class) probability (default args.ece_num_bins,
@@ -1194,33 +1264,53 @@ class _StackedSampler:
         mixture (the form for per_chain sweeps, cf. `evaluate_chains`), every
         value a list of K.  per_example=True adds `per_example`: the [G, N]
         tensors entropy, expected_entropy, mutual_info, confidence, nll, pred
-        and disagree, concatenated over the loader.  This process's chains only."""
-        from . import chains
-        if chains.world() > 1:
-            raise ValueError("uncertainty: the report describes this process's chains only, and "
-                             f"{chains.world()} processes share the predictive (run it in one "
-                             "process, or per process on its own chains before init)")
+        and disagree, concatenated over the loader.  temperature: None (nothing
+        else happens), a float, a length-G sequence or "fitted"
+        (`fit_temperature`'s, of the same by_chain): adds `scaled` = {temperature,
+        nll, ece, mce, entropy, confidence} of softmax(logp / T), from
+        kernels.temper_report on every batch's log mixture — its totals are
+        read in the same single host read.  This process's chains only."""
+        _single_process("uncertainty")
         nb = int(num_bins if num_bins is not None else getattr(self.args, "ece_num_bins", None) or 15)
         dev = self.args.device
         G = self.K if by_chain else 1
         want = K.PREDICT_DEFAULT_WANT if per_example else ()
-        tot, pieces, bufs = None, [], {}
+        tstate = None if temperature is None else self._temperature_state(temperature, by_chain, G)
+        tot, ttot, pieces, bufs = None, None, [], {}
         was = self.net.training
         self.net.eval()
         try:
             for x, y in loader:
-                x, y = x.to(dev), y.to(dev)
+                x, y = x.to(dev), y.to(dev).to(torch.int64).contiguous()
                 lg = self._member_logits(x, bufs)
-                outs, tot = K.predict(lg, y.to(torch.int64).contiguous(), groups=G, totals=tot,
-                                      num_bins=nb, want=want)
+                outs, tot = K.predict(lg, y, groups=G, totals=tot, num_bins=nb,
+                                      want=want if tstate is None else want + ("logp",))
+                if tstate is not None:
+                    ttot = K.temper_report(outs.pop("logp"), y, tstate, groups=G, totals=ttot,
+                                           num_bins=nb)
                 pieces.append(outs)
         finally:
             self.net.train(was)
         if tot is None:
             raise ValueError("uncertainty: the loader is empty")
-        rows = tot.summary()  # the one host read
+        if tstate is None:
+            rows = tot.summary()  # the one host read
+        else:  # ... of both: one buffer, one copy
+            both = torch.cat([tot.buf, ttot.buf, tstate.buf]).cpu().numpy().tobytes()
+            n1, n2 = tot.buf.numel(), ttot.buf.numel()
+            rows = [K.predict_summary(r, tot.members, nb)
+                    for r in np.frombuffer(both[:n1], dtype=np.dtype(L.PredictTotals))]
+            trows = [K.temper_summary(r, nb)
+                     for r in np.frombuffer(both[n1:n1 + n2], dtype=np.dtype(L.TemperTotals))]
+            betas = np.frombuffer(both[n1 + n2:], dtype=np.dtype(L.TemperState))["beta"]
+            for r, beta in zip(trows, betas):
+                r["temperature"] = 1.0 / float(beta)
         res = {k: [r[k] for r in rows] for k in rows[0]} if by_chain else rows[0]
         res["members"], res["num_bins"] = tot.members, nb
+        if tstate is not None:
+            keys = ("temperature", "nll", "ece", "mce", "entropy", "confidence")
+            res["scaled"] = ({k: [r[k] for r in trows] for k in keys} if by_chain
+                             else {k: trows[0][k] for k in keys})
         if per_example:
             res["per_example"] = {w: torch.cat([p[w] for p in pieces], 1) for w in want}
         return res
