@@ -274,15 +274,17 @@ def member_ties(logits):
 # (classes, members, groups, batch, seed).  C: scalar and 16-B paths, fewer
 # classes than lanes, both sides of the wave / workgroup boundary (256 | 257,
 # 260), one trip exactly (1000, 1024), one lane into a second (1028), every
-# trip count of the workgroup instance (1, 2, 4, 8) on both load paths, the
-# limit.  B = 5 on two workgroups gives uneven second trips.
+# trip count of the workgroup instance (1, 2, 4, 8) on both load paths (1030
+# and 2052 complete the ten instances of launch_by_classes: two trips element
+# by element, four in 16-B loads), the limit.  B = 5 on two workgroups gives
+# uneven second trips.
 CASES = [
     (1, 1, 1, 1, 1), (2, 2, 1, 5, 2), (3, 5, 3, 5, 3), (10, 40, 1, 130, 4), (10, 5, 3, 130, 5),
     (10, 1, 1, 130, 6), (37, 2, 1, 130, 7), (37, 1, 3, 5, 8), (255, 2, 1, 5, 9),
     (256, 5, 1, 5, 10), (257, 5, 1, 5, 11), (260, 2, 3, 5, 12), (1000, 40, 1, 5, 13),
     (1000, 5, 3, 130, 14), (1024, 2, 1, 130, 15), (1024, 1, 1, 5, 16), (1028, 5, 1, 130, 17),
     (1028, 2, 3, 1, 18), (2050, 2, 1, 5, 19), (4099, 2, 1, 5, 20), (4100, 2, 1, 5, 21),
-    (8192, 2, 1, 5, 22),
+    (8192, 2, 1, 5, 22), (1030, 2, 1, 5, 23), (2052, 2, 1, 5, 24),
 ]
 NB = 15
 

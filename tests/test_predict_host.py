@@ -163,6 +163,26 @@ def test_input_conditions_of_the_gpu_cases(case):
         assert (r["disagree"][ok] == 0).all()
 
 
+def test_cases_reach_every_instance_of_launch_by_classes():
+    """launch_by_classes' ladder restated (its text is held below): trips 1 on a
+    wave, 1, 2, 4, 8 on a workgroup, each in 16-B loads and element by element."""
+    def instance(Cn):
+        q = (Cn + 3) // 4
+        nt = 1 if Cn <= 256 or q <= 256 else 2 if q <= 512 else 4 if q <= 1024 else 8
+        return nt, Cn % 4 == 0, Cn <= 256
+    flat = " ".join(open(os.path.join(ROOT, "bayesdll_amd", "csrc", "bdl_predict.hip")).read().split())
+    for text in ("if (a.classes <= BDL_PREDICT_WAVE_CLASSES) launch<1, VEC, true>",
+                 "else if (groups4 <= kBlock) launch<1, VEC, false>",
+                 "else if (groups4 <= 2 * kBlock) launch<2, VEC, false>",
+                 "else if (groups4 <= 4 * kBlock) launch<4, VEC, false>",
+                 "else launch<8, VEC, false>"):
+        assert text in flat, text
+    every = {(nt, vec, wave) for nt, wave in ((1, True), (1, False), (2, False), (4, False), (8, False))
+             for vec in (True, False)}
+    assert {instance(c[0]) for c in R.CASES} == every and len(every) == 10
+    assert {instance(c[0]) for c in R.CASES[:22]} == every - {(2, False, False), (4, True, False)}
+
+
 # ------------------------------------------------------- 4. header, ctypes, exports
 ARGS_FIELDS = ["logits", "labels", "logp", "entropy", "expected_entropy", "mutual_info",
                "confidence", "nll", "pred", "disagree", "totals", "workspace", "batch", "members",
