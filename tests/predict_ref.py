@@ -30,7 +30,19 @@ expected_entropy: mean_i b_i + u expected_entropy.  mutual_info: the sum of the
 two, + u |mutual_info|.  Every bound is multiplied by 1.001 for the second-order
 terms and gets 2^-40 for the fp64 sums.  A total's bound is the sum of its
 examples' bounds plus 2^-45 of the sum of the magnitudes (fp64 summation of at
-most 2^8 x ... terms in any order).  Integer outputs have no bound: they are
+most 2^8 x ... terms in any order).  That assumes at most 2^8 terms: n terms
+added in any order, over any number of accumulating calls, take at most
+n - 1 + calls additions, each rounding a partial sum that is at most the sum S
+of the magnitudes by 2^-53, so the error is at most (n - 1 + calls) 2^-53 S.
+check_totals compares up to two passes over the same examples (scale = 2, up
+to four calls): 2 n + 3 additions on magnitudes 2 S against twice this bound,
+which therefore takes (2 n + 4) 2^-53 of S.  A group of more than 2^8 examples
+gets that factor, with n the terms of the sum (of a bin: the probabilities in
+it); up to 2^8 examples the 2^-45 stays as it was (there it covers one
+pass over the five sums, n - 1 < 2^8 additions; for a bin of more than 2^8 probabilities it is not a
+derived bound, and is kept so that the earlier cases' criterion does not
+change — the bin's summed eps is 10^4 times larger).  Integer outputs have no
+bound: they are
 exact PROVIDED no reference probability is within the margin of a decision —
 `margins` reports how far every case is from one, and tests/test_predict_host.py
 asserts 4 x the bound everywhere."""
@@ -168,8 +180,13 @@ def bound(r, labels=None):
     for g, t in enumerate(r["totals"]):
         ok, okl, wrong = t["ok_mask"], t["okl_mask"], t["wrong_mask"]
 
+        many = int(ok.sum()) + t["n_nonfinite"] > 2 ** 8
+
+        def sumf(n):
+            return (2 * n + 4) * 2.0 ** -53 if many else 2.0 ** -45
+
         def tot(b, v, sel):
-            return float(b[g][sel].sum() + 2.0 ** -45 * np.abs(v[g][sel]).sum())
+            return float(b[g][sel].sum() + sumf(int(sel.sum())) * np.abs(v[g][sel]).sum())
         bt = {"nll_sum": tot(bnll, np.nan_to_num(r["nll"], posinf=0.0), okl),
               "entropy_sum": tot(bent, r["entropy64"], ok),
               "expected_entropy_sum": tot(bee, r["expected_entropy64"], ok),
@@ -179,8 +196,9 @@ def bound(r, labels=None):
         rows = np.nonzero(okl)[0]
         if len(rows):
             k = r["bins_of"][g][rows].ravel()
-            w = (eps[g][rows] + 2.0 ** -45 * pbar[g][rows]).ravel()
             nbins = int(k.max()) + 1
+            fk = np.array([sumf(int(n)) for n in np.bincount(k, minlength=nbins)])
+            w = (eps[g][rows].ravel() + fk[k] * pbar[g][rows].ravel())
             bc[:nbins] = np.bincount(k, weights=w, minlength=nbins)
         bt["bin_conf"] = bc
         tots.append(bt)
