@@ -425,6 +425,51 @@ TEMPER_EXPORTS = {
     "bdl_temper_report": (C.c_int, [C.POINTER(TemperReportArgs), C.c_void_p]),
 }
 
+MIXTURE_MAX_CLASSES, MIXTURE_WAVE_CLASSES = 4096, 256
+MIXTURE_MAX_PAIRS, MIXTURE_MAX_GRID = 65535, 1024
+MIXTURE_MIN_WEIGHT = 1e-10
+MIXTURE_RESET = 0x1
+MIX_ARITHMETIC, MIX_REFERENCE = 0, 1
+MIX_COMBINE = {"arithmetic": MIX_ARITHMETIC, "reference": MIX_REFERENCE}
+
+
+class MemberScore(C.Structure):
+    """include/bdl_mixture.h bdl_member_score_t (one per (member, group), device memory)."""
+    _fields_ = [("n", C.c_int64), ("n_nonfinite", C.c_int64), ("n_wrong", C.c_int64),
+                ("nll_sum", C.c_double)]
+
+
+class MemberScoreArgs(C.Structure):
+    """include/bdl_mixture.h bdl_member_score_args."""
+    _fields_ = [("logits", _fp), ("labels", _fp), ("scores", _fp), ("workspace", _fp),
+                ("batch", C.c_int64), ("members", C.c_int32), ("groups", C.c_int32),
+                ("classes", C.c_int32), ("grid_blocks", C.c_int32), ("flags", C.c_int32),
+                ("pad0", C.c_int32)]
+
+
+class MixtureTotals(C.Structure):
+    """include/bdl_mixture.h bdl_mixture_totals (one per group, device memory)."""
+    _fields_ = [("n", C.c_int64), ("n_nonfinite", C.c_int64),
+                ("expected_entropy_sum", C.c_double)]
+
+
+class MixtureArgs(C.Structure):
+    """include/bdl_mixture.h bdl_mixture_args."""
+    _fields_ = [("logits", _fp), ("weights", _fp), ("labels", _fp), ("logp", _fp),
+                ("expected_entropy", _fp), ("totals", _fp), ("workspace", _fp),
+                ("batch", C.c_int64), ("components", C.c_int32), ("draws", C.c_int32),
+                ("groups", C.c_int32), ("classes", C.c_int32), ("combine", C.c_int32),
+                ("grid_blocks", C.c_int32), ("flags", C.c_int32), ("pad0", C.c_int32)]
+
+
+# include/bdl_mixture.h: additive to the ABI, as DIAG_EXPORTS
+MIXTURE_EXPORTS = {
+    "bdl_member_score_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "bdl_mixture_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "bdl_member_score": (C.c_int, [C.POINTER(MemberScoreArgs), C.c_void_p]),
+    "bdl_mixture": (C.c_int, [C.POINTER(MixtureArgs), C.c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -451,7 +496,8 @@ def lib():
                                       + list(LAYERS_EXPORTS.items())
                                       + list(PREDICT_EXPORTS.items())
                                       + list(FN_EXPORTS.items())
-                                      + list(TEMPER_EXPORTS.items())):
+                                      + list(TEMPER_EXPORTS.items())
+                                      + list(MIXTURE_EXPORTS.items())):
                 fn = getattr(h, name)
                 fn.restype = res
                 fn.argtypes = argt

@@ -1162,6 +1162,188 @@ def temper_report(logp, labels, temperature, groups=1, totals=None, num_bins=15,
     return totals
 
 
+def _mixture_rows(what, logits, labels, groups, grid_blocks, pairs_of):
+    """The checks `member_score` and `mixture` share, worded as predict's;
+    returns (members, G, B, C, grid_blocks); pairs_of(members, G) is the
+    number of pairs the sweep's grid has."""
+    if not torch.is_tensor(logits) or logits.dim() < 2:
+        raise ValueError(f"{what}: logits must be a [..., B, C] tensor")
+    L.require_hip(logits, "logits")
+    if not logits.is_contiguous():
+        raise ValueError(f"{what}: logits must be contiguous")
+    G = int(groups)
+    B, Cn = int(logits.shape[-2]), int(logits.shape[-1])
+    lead = logits.numel() // max(B * Cn, 1)
+    if G < 1 or B < 1 or lead < 1 or lead % G:
+        raise ValueError(f"{what}: {tuple(logits.shape)} is not members x groups ({G}) x B x C")
+    if not 1 <= Cn <= L.MIXTURE_MAX_CLASSES:
+        raise ValueError(f"{what}: 1 <= classes <= {L.MIXTURE_MAX_CLASSES} (got {Cn})")
+    M = lead // G
+    pairs = pairs_of(M, G)
+    if not 1 <= pairs <= L.MIXTURE_MAX_PAIRS:
+        raise ValueError(f"{what}: at most {L.MIXTURE_MAX_PAIRS} (member, group) pairs / groups "
+                         f"(got {pairs})")
+    grid = int(grid_blocks)
+    if not 0 <= grid <= L.MIXTURE_MAX_GRID:
+        raise ValueError(f"{what}: grid_blocks in [0, {L.MIXTURE_MAX_GRID}]")
+    dev = logits.device
+    if labels is not None:
+        if (not torch.is_tensor(labels) or labels.dtype != torch.int64 or labels.shape != (B,)
+                or not labels.is_contiguous() or labels.device != dev):
+            raise ValueError(f"{what}: labels must be a contiguous int64 [B] tensor on the logits' "
+                             "device")
+    return M, G, B, Cn, grid
+
+
+def _mixture_grid(grid, B, Cn, pairs, dev):
+    """grid_blocks, or the library's default (so that the workspace is sized
+    for it): one workgroup per row slot of a pair, up to four per CU over all
+    pairs."""
+    if grid:
+        return grid
+    slots = -(-B // (4 if Cn <= L.MIXTURE_WAVE_CLASSES else 1))
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    return max(1, min(slots, -(-4 * cus // pairs), L.MIXTURE_MAX_GRID))
+
+
+class MemberScores:
+    """The running loss sums of `member_score` calls: bdl_member_score_t
+    [members, groups] in device memory.  `read()` is the one host read (a
+    structured [members, groups] array with the struct's fields)."""
+
+    def __init__(self, members, groups, device):
+        self.members, self.groups = int(members), int(groups)
+        self.buf = torch.empty(self.members * self.groups * C.sizeof(L.MemberScore),
+                               dtype=torch.uint8, device=device)
+        self.fresh = True  # nothing accumulated: the first call resets
+
+    def read(self):
+        if self.fresh:
+            raise ValueError("member_score: these scores hold nothing yet")
+        raw = np.frombuffer(self.buf.cpu().numpy().tobytes(), dtype=np.dtype(L.MemberScore))
+        return raw.reshape(self.members, self.groups)
+
+
+def member_score(logits, labels, *, groups, scores=None, reset=False, grid_blocks=0):
+    """The likelihood pass of a cycle end in one fused sweep per batch
+    (bdl_member_score, include/bdl_mixture.h: the arithmetic contract): the
+    cross-entropy sum, the scored, wrong and non-finite row counts of every
+    (member, group) pair of fp32 logits [..., B, C] (leading dimensions
+    flattening to members x groups) against int64 labels [B], ADDED to the
+    MemberScores handle (a new one, or the one passed in; reset=True overwrites
+    it).  Two launches on the current stream, no host read here:
+    scores.read() is the one."""
+    if labels is None:
+        raise ValueError("member_score: labels must be a contiguous int64 [B] tensor on the "
+                         "logits' device")
+    M, G, B, Cn, grid = _mixture_rows("member_score", logits, labels, groups, grid_blocks,
+                                      lambda m, g: m * g)
+    dev = logits.device
+    if scores is None:
+        scores = MemberScores(M, G, dev)
+    elif (scores.members, scores.groups) != (M, G) or scores.buf.device != dev:
+        raise ValueError("member_score: these scores were started with other members / groups or "
+                         "on another device")
+    grid = _mixture_grid(grid, B, Cn, M * G, dev)
+    nbytes = int(L.lib().bdl_member_score_workspace_bytes(M, G, grid))
+    ws = _scratch(("member_score", dev.index, nbytes),
+                  lambda: torch.empty(nbytes, dtype=torch.uint8, device=dev))
+    a = L.MemberScoreArgs()
+    a.logits, a.labels = logits.data_ptr(), labels.data_ptr()
+    a.scores, a.workspace = scores.buf.data_ptr(), ws.data_ptr()
+    a.batch, a.members, a.groups, a.classes, a.grid_blocks = B, M, G, Cn, grid
+    a.flags = L.MIXTURE_RESET if (reset or scores.fresh) else 0
+    L.check(L.lib().bdl_member_score(a, L.current_stream_handle(dev)), "bdl_member_score")
+    scores.fresh = False
+    return scores
+
+
+MIXTURE_OUTPUTS = ("logp", "expected_entropy")
+
+
+class MixtureTotals:
+    """The running totals of `mixture` calls: bdl_mixture_totals[groups] in
+    device memory.  `read()` is the one host read (a structured array with the
+    struct's fields), `summary()` one dict per group: n, n_nonfinite,
+    expected_entropy (the mean; NaN over nothing)."""
+
+    def __init__(self, groups, device):
+        self.groups = int(groups)
+        self.buf = torch.empty(self.groups * C.sizeof(L.MixtureTotals), dtype=torch.uint8,
+                               device=device)
+        self.fresh = True  # nothing accumulated: the first call resets
+
+    def read(self):
+        if self.fresh:
+            raise ValueError("mixture: these totals hold nothing yet")
+        return np.frombuffer(self.buf.cpu().numpy().tobytes(), dtype=np.dtype(L.MixtureTotals))
+
+    def summary(self):
+        return [mixture_summary(r) for r in self.read()]
+
+
+def mixture_summary(row):
+    n = int(row["n"])
+    return {"n": n, "n_nonfinite": int(row["n_nonfinite"]),
+            "expected_entropy": float(row["expected_entropy_sum"]) / n if n else float("nan")}
+
+
+def mixture(logits, weights, labels=None, *, draws, groups, combine="arithmetic",
+            want=("logp",), totals=None, reset=False, grid_blocks=0):
+    """The weighted predictive of a mixture of components in one fused sweep
+    (bdl_mixture, include/bdl_mixture.h: the definitions and the arithmetic
+    contract).  logits: fp32, contiguous [..., B, C] whose leading dimensions
+    flatten to (components x draws) x groups — member c * draws + s is draw s
+    of component c.  weights: float64 [components, groups] on the device, taken
+    as given; a component below 1e-10 is skipped and its rows are not read.
+    combine: "arithmetic" (log of the weighted mean probability) or
+    "reference" (a cyclical Runner's renormalised weighted sum of component
+    log-probabilities).  labels: accepted as predict takes them, not read.
+    Returns (outs, totals): outs[w] for w in want — `logp` [G, B, C],
+    `expected_entropy` [G, B] — and the MixtureTotals handle the call ADDED to
+    (reset=True overwrites it).  Two launches on the current stream, no host
+    read here: totals.read() / .summary() is the one."""
+    want = tuple(want)
+    if any(w not in MIXTURE_OUTPUTS for w in want):
+        raise ValueError(f"mixture: want from {MIXTURE_OUTPUTS}")
+    if combine not in L.MIX_COMBINE:
+        raise ValueError(f"mixture: combine from {tuple(L.MIX_COMBINE)} (got {combine!r})")
+    M, G, B, Cn, grid = _mixture_rows("mixture", logits, labels, groups, grid_blocks,
+                                      lambda m, g: g)
+    D = int(draws)
+    if D < 1 or M % D:
+        raise ValueError(f"mixture: {M} members are not components x draws ({D})")
+    comps, dev = M // D, logits.device
+    if (not torch.is_tensor(weights) or weights.dtype != torch.float64
+            or tuple(weights.shape) != (comps, G) or not weights.is_contiguous()
+            or weights.device != dev):
+        raise ValueError(f"mixture: weights must be a contiguous float64 [{comps}, {G}] tensor on "
+                         "the logits' device")
+    if totals is None:
+        totals = MixtureTotals(G, dev)
+    elif totals.groups != G or totals.buf.device != dev:
+        raise ValueError("mixture: these totals were started with other groups or on another "
+                         "device")
+    grid = _mixture_grid(grid, B, Cn, G, dev)
+    nbytes = int(L.lib().bdl_mixture_workspace_bytes(G, grid))
+    ws = _scratch(("mixture", dev.index, nbytes),
+                  lambda: torch.empty(nbytes, dtype=torch.uint8, device=dev))
+    outs = {w: torch.empty((G, B, Cn) if w == "logp" else (G, B), device=dev, dtype=torch.float32)
+            for w in want}
+    a = L.MixtureArgs()
+    a.logits, a.weights = logits.data_ptr(), weights.data_ptr()
+    a.labels = None if labels is None else labels.data_ptr()
+    for w in MIXTURE_OUTPUTS:
+        setattr(a, w, outs[w].data_ptr() if w in outs else None)
+    a.totals, a.workspace = totals.buf.data_ptr(), ws.data_ptr()
+    a.batch, a.components, a.draws, a.groups, a.classes = B, comps, D, G, Cn
+    a.combine, a.grid_blocks = L.MIX_COMBINE[combine], grid
+    a.flags = L.MIXTURE_RESET if (reset or totals.fresh) else 0
+    L.check(L.lib().bdl_mixture(a, L.current_stream_handle(dev)), "bdl_mixture")
+    totals.fresh = False
+    return outs, totals
+
+
 def clip_bytes_per_elem(clipped_share=1.0):
     """Algorithmic HBM bytes per gradient element of one chain_clip call
     (DESIGN §4e): every element read once for the norm; the elements of the

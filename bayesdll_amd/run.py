@@ -143,6 +143,13 @@ def build_parser():
                          "entropy, mutual information (overall, on wrong against other examples) "
                          "and member disagreement from one fused sweep over the members' logits "
                          "(stacked uncertainty()); per chain with --sweep")
+    ap.add_argument("--gmm_weights", action="store_true",
+                    help="with --stacked_chains >= 1 and a cyclical method: at every cycle end, "
+                         "score max(1, nst) posterior draws of all chains on the training set "
+                         "(stacked score_cycle(): one fused sweep per batch, one host read), log "
+                         "every chain's GMM component weights and add the likelihood-weighted "
+                         "mixture's NLL and error to the epoch record (test_gmm; per chain with "
+                         "--sweep: chains_gmm)")
     ap.add_argument("--temperature_scale", action="store_true",
                     help="with --stacked_chains >= 1 and --val_heldout > 0: after training, fit a "
                          "scalar temperature to the stacked predictive on the validation split "
@@ -197,6 +204,18 @@ def check_uncertainty(ap, args):
         ap.error("--uncertainty reports the stacked chains' predictive: it needs "
                  "--stacked_chains >= 1")
     return args.uncertainty
+
+
+def check_gmm_weights(ap, args):
+    """--gmm_weights needs stacked chains of a cyclical method (ap.error
+    otherwise)."""
+    if args.gmm_weights and args.stacked_chains < 1:
+        ap.error("--gmm_weights weighs the stacked chains' cycles: it needs --stacked_chains >= 1 "
+                 "(a one-chain cyclical Runner always weighs its cycles)")
+    if args.gmm_weights and args.method not in ("csghmc", "csgld", "adam_csghmc"):
+        ap.error(f"--gmm_weights weighs the cycles of a cyclical method (csghmc, csgld, "
+                 f"adam_csghmc), not {args.method}")
+    return args.gmm_weights
 
 
 def check_temperature_scale(ap, args):
@@ -359,6 +378,7 @@ def main(argv=None):
     check_health(ap, args)
     check_ess(ap, args)
     check_uncertainty(ap, args)
+    check_gmm_weights(ap, args)
     check_temperature_scale(ap, args)
     check_by_tensor(ap, args)
     check_fn(ap, args)

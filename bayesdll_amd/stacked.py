@@ -357,6 +357,37 @@ def _single_process(what):
                          "process, or per process on its own chains before init)")
 
 
+def cycle_weights(cycle_likelihoods, keys, by_chain=True):
+    """float64 [len(keys), K] mixture weights of the cycles `keys` from
+    {cycle: float64 [draws, K] likelihoods} (score_cycle).  by_chain=True: every
+    chain gets the reference's w_c = 1 / mean_j(1 / lik_j), normalised over ITS
+    cycles (_runner.gmm_weights on the chain's column: K Runners).
+    by_chain=False: normalised jointly over all (cycle, chain), as
+    chains.chain_gmm_weights does over processes; uniform when no weight is
+    positive."""
+    from ._runner import gmm_weights
+    keys = list(keys)
+    if not keys:
+        raise ValueError("component_weights: nothing is collected yet")
+    for c in keys:
+        if c not in cycle_likelihoods:
+            raise ValueError(f"component_weights: cycle {c} has not been scored (score_cycle)")
+    lik = {c: np.asarray(cycle_likelihoods[c], dtype=np.float64) for c in keys}
+    K_ = lik[keys[0]].shape[1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if by_chain:
+            out = np.empty((len(keys), K_), dtype=np.float64)
+            for k in range(K_):
+                w = gmm_weights({c: list(lik[c][:, k]) for c in keys})
+                out[:, k] = [w[c] for c in keys]
+            return out
+        raw = np.stack([1.0 / np.mean(1.0 / lik[c], axis=0) for c in keys])
+    tot = raw.sum()
+    if not tot > 0:
+        return np.full(raw.shape, 1.0 / raw.size)
+    return raw / tot
+
+
 class _StackedSampler:
     """What every stacked sampler shares: K chains' state, the vmapped
     forward/backward (optionally replayed from a HIP graph), the predictive
@@ -376,6 +407,13 @@ class _StackedSampler:
     per_chain_family = None
     per_chain = None   # {name: float64 [K]} over the family's names, or None (uniform)
     swept = ()         # the names the caller gave
+
+    # the likelihood-weighted cycle mixture (cyclical samplers): score every
+    # finished cycle in train() (args.gmm_weights), and {cycle: float64
+    # [draws, K] likelihoods} of `score_cycle`
+    cyclical = False
+    gmm_weights = False
+    cycle_likelihoods = None
 
     def _init_per_chain(self, per_chain, K_, args):
         """Validate `per_chain` before anything touches the device."""
@@ -400,6 +438,12 @@ class _StackedSampler:
         refuse_compute_dtype(getattr(args, "compute_dtype", None) or default_compute_dtype(),
                              "the stacked samplers (bayesdll_amd.stacked)")
         self._init_per_chain(per_chain, K_, args)
+        self.gmm_weights = bool(getattr(args, "gmm_weights", False))
+        if self.gmm_weights and not self.cyclical:
+            raise ValueError(f"{type(self).__name__}: gmm_weights weighs the cycles of a cyclical "
+                             "sampler (StackedCSGHMC, StackedCSGLD, StackedAdamCSGHMC); this one "
+                             "collects one component")
+        self.cycle_likelihoods = {}
         if int(health_every) != health_every or int(health_every) < 0:
             raise ValueError(f"health_every must be an integer >= 0 (got {health_every!r})")
         # batch length b of the batch-means ESS accumulators every collected
@@ -1011,12 +1055,16 @@ class _StackedSampler:
             lp = torch.stack(self._component_logprobs(x), 0).double()  # [components, K, B, C]
             return lp.logsumexp(0) - math.log(lp.shape[0])
 
-    def evaluate_chains(self, loader):
+    def evaluate_chains(self, loader, weights=None, combine="arithmetic"):
         """(nll [K], err [K]) over a data loader, chain by chain: each chain is
         scored from its own collected components (the draws and keys
         `_components` uses) or from its current theta while nothing is
         collected.  What ranks a per_chain sweep; applies to any stacked
-        sampler.  One host read at the end."""
+        sampler.  One host read at the end.  weights="gmm" (cyclical samplers):
+        every chain's cycles weighted by `component_weights(by_chain=True)`,
+        combined as `combine` says (kernels.mixture) — K Runners."""
+        if weights is not None:
+            return self._weighted_scores("evaluate_chains", loader, weights, combine, True)
         dev = self.args.device
         nll = torch.zeros(self.K, dtype=torch.float64, device=dev)
         err = torch.zeros(self.K, dtype=torch.int64, device=dev)
@@ -1145,9 +1193,14 @@ class _StackedSampler:
                                                  "share_above")
         return out
 
-    def evaluate(self, loader):
+    def evaluate(self, loader, weights=None, combine="arithmetic"):
         """(NLL, error) of the stacked predictive over a data loader (the
-        network in eval mode, as the reference's evaluate)."""
+        network in eval mode, as the reference's evaluate).  weights="gmm"
+        (cyclical samplers): the (cycle, chain) components weighted jointly by
+        `component_weights(by_chain=False)` (kernels.mixture)."""
+        if weights is not None:
+            nll, err = self._weighted_scores("evaluate", loader, weights, combine, False)
+            return float(nll[0]), float(err[0])
         dev = self.args.device
         loss, err, nb = 0.0, 0, 0
         was = self.net.training
@@ -1163,13 +1216,16 @@ class _StackedSampler:
             self.net.train(was)
         return loss / nb, err / nb
 
-    def _member_logits(self, x, bufs):
+    def _member_logits(self, x, bufs, pooled=False):
         """[members, K, B, C] raw logits of the members `_component_logprobs`
         averages over — the same draws in the same order from the same keys,
         or the chains' current theta while nothing is collected — written into
-        one buffer per batch shape (kept in `bufs`)."""
+        one buffer per batch shape (kept in `bufs`).  pooled (the weighted
+        mixture over all chains): [components, K, draws, B, C], so that the
+        (cycle, chain) pairs are the contiguous components of one group."""
         st = self.state
-        n = len(self._component_keys()) * max(1, self.nst)
+        nd = max(1, self.nst)
+        n = len(self._component_keys()) * nd
         with torch.no_grad():
             if n == 0:
                 return self.chain_logits(x).float().contiguous().unsqueeze(0)
@@ -1181,20 +1237,198 @@ class _StackedSampler:
                 lg = self._fwd(views, x)
                 if out is None:
                     key = (n,) + tuple(lg.shape)
+                    if pooled:
+                        key = (n // nd, self.K, nd) + tuple(lg.shape[1:])
                     out = bufs.get(key)
                     if out is None:
                         out = bufs[key] = torch.empty(key, dtype=torch.float32, device=lg.device)
-                out[i].copy_(lg)
+                if pooled:
+                    out[i // nd, :, i % nd].copy_(lg)
+                else:
+                    out[i].copy_(lg)
             return out
+
+    # ------------------------------------- likelihood-weighted cycle mixture
+    def score_cycle(self, train_loader, c=None):
+        """The reference's cycle-end likelihood pass (methods/csghmc.py:568-638)
+        for all K chains at once: max(1, nst) posterior draws of every chain
+        from cycle c's moments (`_moment_spec`; the latest collected cycle by
+        default; with nst = 0 the means), the vmapped forward in eval mode over
+        the loader, kernels.member_score per batch with groups = K — the loss
+        sums stay on the device until ONE host read at the end.  Stores and
+        returns cycle_likelihoods[c]: float64 [draws, K] of exp(-nll_sum / n)."""
+        self._need_cyclical("score_cycle")
+        c = self._latest_component() if c is None else c
+        m1, m2, var_mode, ratio, _ = self._moment_spec(c) if c is not None else (None,) * 5
+        if m1 is None:
+            raise ValueError(f"score_cycle: cycle {c} is not collected")
+        st, dev, nd = self.state, self.args.device, max(1, self.nst)
+        scores, out = None, {}
+        was = self.net.training
+        self.net.eval()
+        try:
+            with torch.no_grad():
+                views = []
+                for _ in range(nd):
+                    buf = torch.empty_like(st.theta)
+                    if self.nst == 0:
+                        buf.copy_(m1)
+                    else:
+                        self._sample(buf, m1, m2, var_mode, ratio)
+                    views.append({nm: buf.view(self.K, st.stride)[:, o:o + k].view(self.K, *s)
+                                  for nm, o, k, s in zip(st.names, st.offsets, st.numels,
+                                                         st.shapes)})
+                for x, y in train_loader:
+                    x, y = x.to(dev), y.to(dev).to(torch.int64).contiguous()
+                    for s, v in enumerate(views):
+                        lg = self._fwd(v, x)
+                        key = (nd,) + tuple(lg.shape)
+                        if key not in out:
+                            out[key] = torch.empty(key, dtype=torch.float32, device=lg.device)
+                        out[key][s].copy_(lg)
+                    scores = K.member_score(out[key], y, groups=self.K, scores=scores)
+        finally:
+            self.net.train(was)
+        if scores is None:
+            raise ValueError("score_cycle: the loader is empty")
+        r = scores.read()  # the one host read
+        with np.errstate(divide="ignore", invalid="ignore"):
+            lik = np.exp(-r["nll_sum"] / r["n"])
+        self.cycle_likelihoods[c] = lik.astype(np.float64)
+        return self.cycle_likelihoods[c]
+
+    def component_weights(self, by_chain=True):
+        """float64 [components, K] weights of the collected cycles
+        (`cycle_weights`): per chain (K Runners) or, by_chain=False, jointly
+        over all (cycle, chain).  Raises, naming the cycle, if a collected
+        cycle has not been scored."""
+        self._need_cyclical("component_weights")
+        return cycle_weights(self.cycle_likelihoods or {}, self._component_keys(), by_chain)
+
+    def _need_cyclical(self, what):
+        if not self.cyclical:
+            raise ValueError(f"{what}: {type(self).__name__} is not cyclical (it collects one "
+                             "component: there are no cycles to weigh)")
+
+    def _mixture_weights(self, what, weights, combine, by_chain):
+        """Every refusal of the weights= / combine= keywords, then the device
+        table kernels.mixture takes: float64 [components, K] by chain,
+        [components * K, 1] pooled."""
+        from . import chains
+        if weights != "gmm":
+            raise ValueError(f'{what}: weights is None (uniform) or "gmm" (got {weights!r})')
+        if combine not in L.MIX_COMBINE:
+            raise ValueError(f"{what}: combine from {tuple(L.MIX_COMBINE)} (got {combine!r})")
+        self._need_cyclical(f'{what}: weights="gmm"')
+        if chains.world() > 1:
+            raise ValueError(f'{what}: weights="gmm" weighs this process\'s chains only, and '
+                             f"{chains.world()} processes share the predictive")
+        if not by_chain and self.per_chain is not None:
+            raise ValueError(f'{what}: weights="gmm" over all chains would weigh different models '
+                             "against each other (per_chain hyperparameters); use the by-chain "
+                             "form")
+        if not by_chain and combine == "reference":
+            raise ValueError(f'{what}: combine="reference" is one Runner\'s rule (a weighted sum '
+                             "of ITS cycles' log-probabilities); it is defined by chain, not over "
+                             "pooled (cycle, chain) components")
+        w = self.component_weights(by_chain)
+        if not by_chain:
+            w = w.reshape(-1, 1)
+        return torch.from_numpy(np.ascontiguousarray(w)).to(self.args.device)
+
+    def _weighted_batches(self, what, loader, weights, combine, by_chain, want=("logp",)):
+        """Per batch of the loader (eval mode): (mixture outputs, labels,
+        MixtureTotals) of the weighted predictive — `evaluate`'s members, the
+        same Philox keys and the same advance of `draws`."""
+        wdev = self._mixture_weights(what, weights, combine, by_chain)
+        dev, nd, bufs, tot = self.args.device, max(1, self.nst), {}, None
+        was = self.net.training
+        self.net.eval()
+        try:
+            for x, y in loader:
+                x, y = x.to(dev), y.to(dev).to(torch.int64).contiguous()
+                lg = self._member_logits(x, bufs, pooled=not by_chain)
+                outs, tot = K.mixture(lg, wdev, y, draws=nd, groups=self.K if by_chain else 1,
+                                      combine=combine, want=want, totals=tot)
+                yield outs, y, tot
+        finally:
+            self.net.train(was)
+
+    def _weighted_scores(self, what, loader, weights, combine, by_chain):
+        """(nll [G], err [G]) of the weighted logp over the loader; one host
+        read at the end."""
+        G, dev = self.K if by_chain else 1, self.args.device
+        nll = torch.zeros(G, dtype=torch.float64, device=dev)
+        err = torch.zeros(G, dtype=torch.int64, device=dev)
+        nb = 0
+        for outs, y, _ in self._weighted_batches(what, loader, weights, combine, by_chain):
+            lp = outs["logp"]
+            nll -= lp.gather(-1, y.view(1, -1, 1).expand(G, -1, 1)).squeeze(-1).double().sum(-1)
+            err += lp.argmax(-1).ne(y).sum(-1)
+            nb += len(y)
+        if nb == 0:
+            raise ValueError(f"{what}: the loader is empty")
+        both = torch.stack([nll, err.double()]).cpu().numpy() / nb
+        return both[0], both[1]
+
+    def _gmm_state(self):
+        """cycle_likelihoods for `_extra_state`, only when the option is on."""
+        if not self.gmm_weights:
+            return {}
+        return {"cycle_likelihoods": {int(c): torch.from_numpy(np.array(v, dtype=np.float64))
+                                      for c, v in self.cycle_likelihoods.items()}}
+
+    def _load_gmm_state(self, d):
+        """... and back; a checkpoint without it loads with nothing scored."""
+        self.cycle_likelihoods = {int(c): v.cpu().numpy().astype(np.float64)
+                                  for c, v in (d.get("cycle_likelihoods") or {}).items()}
+
+    def _report_gmm(self, ep, rec, train_loader, test_loader, log):
+        """run.py --gmm_weights: score the finished cycle, log every chain's
+        `GMM component weights: {...}` line (the reference's), and with a test
+        loader the weighted NLL and error under rec["test_gmm"] (per chain
+        under per_chain: rec["chains_gmm"])."""
+        try:
+            c = self._latest_component()
+            self.score_cycle(train_loader, c)
+            w = self.component_weights(by_chain=True)
+            keys = self._component_keys()
+            rec["gmm_weights"] = {"cycles": [int(k) for k in keys], "weights": w.tolist()}
+            for k in range(self.K):
+                log(f"(Epoch {ep}) chain {self.chain0 + k}: GMM component weights: "
+                    f"{ {int(c): float(w[i, k]) for i, c in enumerate(keys)} }")
+            if test_loader is None:
+                return
+            if self.per_chain is None:
+                rec["test_gmm"] = self.evaluate(test_loader, weights="gmm")
+                log(f"(Epoch {ep}) stacked predictive, GMM weights: loss = "
+                    f"{rec['test_gmm'][0]:.4f}, error = {rec['test_gmm'][1]:.4f}")
+            else:
+                nll, err = self.evaluate_chains(test_loader, weights="gmm")
+                rec["chains_gmm"] = {"nll": nll.tolist(), "error": err.tolist()}
+                for k in range(self.K):
+                    log(f"(Epoch {ep}) chain {self.chain0 + k}, GMM weights: loss = {nll[k]:.4f}, "
+                        f"error = {err[k]:.4f}")
+        except ValueError as e:
+            log(f"(Epoch {ep}) GMM weights: {e}")
 
     temperature_ = None   # fit_temperature's [G] device tensor (not checkpointed)
     _temper = None        # (by_chain, kernels.TemperState) of the last fit
 
-    def _loader_logp(self, loader, G):
+    def _loader_logp(self, loader, G, weights=None, combine="arithmetic", by_chain=False):
         """(logp [G, N, C], labels [N]) of `evaluate`'s members over the loader,
-        both on the device: predict's log mixture per batch, concatenated."""
+        both on the device: predict's log mixture per batch, concatenated (the
+        weighted mixture's with weights="gmm")."""
         dev = self.args.device
         lps, ys, bufs = [], [], {}
+        if weights is not None:
+            for outs, y, _ in self._weighted_batches("fit_temperature", loader, weights, combine,
+                                                     by_chain):
+                lps.append(outs["logp"])
+                ys.append(y)
+            if not lps:
+                return None, None
+            return torch.cat(lps, 1).contiguous(), torch.cat(ys).contiguous()
         was = self.net.training
         self.net.eval()
         try:
@@ -1209,7 +1443,8 @@ class _StackedSampler:
             return None, None
         return torch.cat(lps, 1).contiguous(), torch.cat(ys).contiguous()
 
-    def fit_temperature(self, loader, *, by_chain=False, rtol=1e-6, max_iter=32):
+    def fit_temperature(self, loader, *, by_chain=False, rtol=1e-6, max_iter=32, weights=None,
+                        combine="arithmetic"):
         """Fit one scalar temperature (per chain with by_chain=True) to the
         stacked predictive on a held-out loader, on the device: T minimises the
         NLL of softmax(logp / T), logp the sample-averaged log-probabilities of
@@ -1221,10 +1456,12 @@ class _StackedSampler:
         temperature="fitted")` and returns the fit's summary (temperature,
         nll_before, nll_after, iterations, converged, at_bound, degenerate, n,
         n_nonfinite, n_inf_label; lists of K under by_chain).  Not part of
-        state_dict.  This process's chains only."""
+        state_dict.  This process's chains only.  weights="gmm" (cyclical
+        samplers) fits on the likelihood-weighted mixture's logp instead
+        (`combine` as kernels.mixture takes it)."""
         _single_process("fit_temperature")
         G = self.K if by_chain else 1
-        logp, y = self._loader_logp(loader, G)
+        logp, y = self._loader_logp(loader, G, weights, combine, by_chain)
         if logp is None:
             raise ValueError("fit_temperature: the loader is empty")
         state = K.temper_fit(logp, y, groups=G, rtol=rtol, max_iter=max_iter)
@@ -1248,7 +1485,7 @@ class _StackedSampler:
         return K.TemperState(K.temper_betas(temperature, G), self.args.device)
 
     def uncertainty(self, loader, *, by_chain=False, num_bins=None, per_example=False,
-                    temperature=None):
+                    temperature=None, weights=None, combine="arithmetic"):
         """What the ensemble is for, over a data loader (the network in eval
         mode, as `evaluate`): NLL, error, ECE / MCE over `num_bins` confidence
         bins of every (example, class) probability (default args.ece_num_bins,
@@ -1269,9 +1506,19 @@ class _StackedSampler:
         (`fit_temperature`'s, of the same by_chain): adds `scaled` = {temperature,
         nll, ece, mce, entropy, confidence} of softmax(logp / T), from
         kernels.temper_report on every batch's log mixture — its totals are
-        read in the same single host read.  This process's chains only."""
+        read in the same single host read.  This process's chains only.
+        weights="gmm" (cyclical samplers): the likelihood-weighted cycle
+        mixture instead (kernels.mixture, `combine` as it takes it) — nll,
+        error, ece, mce, entropy and confidence from kernels.temper_report at
+        T = 1 on the weighted logp, expected_entropy and mutual_info = entropy
+        - expected_entropy from the mixture's totals, one host read;
+        disagreement is not defined under weights and is omitted, and
+        per_example / temperature are not offered there."""
         _single_process("uncertainty")
         nb = int(num_bins if num_bins is not None else getattr(self.args, "ece_num_bins", None) or 15)
+        if weights is not None:
+            return self._weighted_uncertainty(loader, by_chain, nb, per_example, temperature,
+                                              weights, combine)
         dev = self.args.device
         G = self.K if by_chain else 1
         want = K.PREDICT_DEFAULT_WANT if per_example else ()
@@ -1313,6 +1560,34 @@ class _StackedSampler:
                              else {k: trows[0][k] for k in keys})
         if per_example:
             res["per_example"] = {w: torch.cat([p[w] for p in pieces], 1) for w in want}
+        return res
+
+    def _weighted_uncertainty(self, loader, by_chain, nb, per_example, temperature, weights,
+                              combine):
+        if per_example or temperature is not None:
+            raise ValueError('uncertainty: weights="gmm" reports the totals at T = 1 only '
+                             "(no per_example, no temperature)")
+        G, tstate, ttot, mtot = self.K if by_chain else 1, None, None, None
+        for outs, y, mtot in self._weighted_batches("uncertainty", loader, weights, combine,
+                                                    by_chain, want=("logp", "expected_entropy")):
+            if tstate is None:
+                tstate = K.TemperState(K.temper_betas(1.0, G), self.args.device)
+            ttot = K.temper_report(outs["logp"], y, tstate, groups=G, totals=ttot, num_bins=nb)
+        if ttot is None:
+            raise ValueError("uncertainty: the loader is empty")
+        both = torch.cat([ttot.buf, mtot.buf]).cpu().numpy().tobytes()  # the one host read
+        n1 = ttot.buf.numel()
+        rows = []
+        for t, m in zip(np.frombuffer(both[:n1], dtype=np.dtype(L.TemperTotals)),
+                        np.frombuffer(both[n1:], dtype=np.dtype(L.MixtureTotals))):
+            r = K.temper_summary(t, nb)
+            r["expected_entropy"] = K.mixture_summary(m)["expected_entropy"]
+            r["mutual_info"] = r["entropy"] - r["expected_entropy"]
+            rows.append(r)
+        res = {k: [r[k] for r in rows] for k in rows[0]} if by_chain else rows[0]
+        comps = len(self._component_keys())
+        res["members"] = comps * max(1, self.nst) * (1 if by_chain else self.K)
+        res["num_bins"], res["combine"] = nb, combine
         return res
 
     def _report_uncertainty(self, ep, rec, loader, log):
@@ -1407,6 +1682,9 @@ class _StackedSampler:
                 log(f"[Epoch {ep}] clip_grad {self.clip_grad:g}: {rec['clip']['clipped']} of "
                     f"{self.K} chains clipped at the last step, largest gradient norm = "
                     f"{rec['clip']['max_norm']:.4g}")
+            if self.gmm_weights and self._evaluate_after(ep, train_loader):
+                # opt-in (run.py --gmm_weights): before the evaluation, as the reference
+                self._report_gmm(ep, rec, train_loader, test_loader, log)
             if test_loader is not None and self._evaluate_after(ep, train_loader):
                 rec["test"] = self.evaluate(test_loader)
                 log(f"(Epoch {ep}) stacked predictive: loss = {rec['test'][0]:.4f}, "
@@ -1480,6 +1758,7 @@ class StackedCSGHMC(_StackedSampler):
                                        self.sched.proportion_exploration)
 
     per_chain_family = "csghmc"
+    cyclical = True
 
     def chain_rows(self, lr):
         """[..., K, 12] fp32 scalar rows for body lrs `lr` ([..., K] float64)."""
@@ -1598,12 +1877,13 @@ class StackedCSGHMC(_StackedSampler):
 
     def _extra_state(self):
         return {"samples_per_cycle": dict(self.samples_per_cycle), "mom1": dict(self.mom1),
-                "mom2": dict(self.mom2), "epoch": self.sched.current_epoch}
+                "mom2": dict(self.mom2), "epoch": self.sched.current_epoch, **self._gmm_state()}
 
     def _load_extra_state(self, d):
         self.samples_per_cycle = dict(d["samples_per_cycle"])
         self.mom1, self.mom2 = dict(d["mom1"]), dict(d["mom2"])
         self.sched.current_epoch = d["epoch"]
+        self._load_gmm_state(d)
 
     def export_chain(self, k, epoch=None):
         """Chain k as a one-chain csghmc checkpoint (the keys of
@@ -1764,6 +2044,8 @@ class StackedCSGLD(StackedSGLD):
     args.clip_grad included (:250-253): every chain is clipped by the norm of
     its own sampler gradient (`_clip_chains`)."""
 
+    cyclical = True
+
     def __init__(self, net, K_, args, **kw):
         super().__init__(net, K_, args, **kw)
         self.burnin = -1  # cSGLD collects per cycle, not after a burn-in
@@ -1842,12 +2124,13 @@ class StackedCSGLD(StackedSGLD):
     def _extra_state(self):
         return {"samples_per_cycle": dict(self.samples_per_cycle), "mom1": dict(self.mom1),
                 "mom2": dict(self.mom2), "has_buffer": self.has_buffer,
-                "epoch": self.sched.current_epoch}
+                "epoch": self.sched.current_epoch, **self._gmm_state()}
 
     def _load_extra_state(self, d):
         self.samples_per_cycle = dict(d["samples_per_cycle"])
         self.mom1, self.mom2 = dict(d["mom1"]), dict(d["mom2"])
         self.has_buffer, self.sched.current_epoch = d["has_buffer"], d["epoch"]
+        self._load_gmm_state(d)
 
 
 class StackedSGHMC(StackedSGLD):
