@@ -266,6 +266,15 @@ def excluded_share(r):
     return float((ok & ~np.isfinite(r["b_logp"])).sum()) / max(int(ok.sum()), 1)
 
 
+def unchecked_share(r):
+    """The share of a case's logp entries of finite examples that check_mixture
+    compares with nothing: without a bound and not -inf in the reference (an
+    entry whose reference is -inf is compared exactly)."""
+    ok = np.broadcast_to(~r["nonfinite"][..., None], r["logp"].shape)
+    checked = np.isfinite(r["b_logp"]) | np.isneginf(r["logp"])
+    return float((ok & ~checked).sum()) / max(int(ok.sum()), 1)
+
+
 def check_mixture(got, r, what, scale=1):
     """Per-example outputs (those present in `got`) and, with got["totals"],
     the totals against the reference within the bound; integers exact; an
