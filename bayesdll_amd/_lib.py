@@ -470,6 +470,31 @@ MIXTURE_EXPORTS = {
     "bdl_mixture": (C.c_int, [C.POINTER(MixtureArgs), C.c_void_p]),
 }
 
+RANK_U, RANK_ITILE, RANK_JTILE, RANK_MAX_ROWS = 2, 512, 1024, 65535
+RANK_MAX_N = 2 ** 31 - 1
+
+
+class RankTotals(C.Structure):
+    """include/bdl_rank.h bdl_rank_totals (one per row, device memory)."""
+    _fields_ = [("n_pos", C.c_int64), ("n_neg", C.c_int64), ("n_excluded", C.c_int64),
+                ("u2", C.c_int64), ("fp_at_tpr", C.c_int64), ("ap_sum", C.c_double)]
+
+
+class RankArgs(C.Structure):
+    """include/bdl_rank.h bdl_rank_args."""
+    _fields_ = [("scores", _fp), ("marks", _fp), ("ge_pos", _fp), ("ge_neg", _fp),
+                ("gt_neg", _fp), ("totals", _fp), ("workspace", _fp), ("n", C.c_int64),
+                ("need", C.c_int64), ("rows", C.c_int32), ("scores_per_group", C.c_int32),
+                ("mark_rows", C.c_int32), ("tpr_num", C.c_int32), ("tpr_den", C.c_int32),
+                ("pad0", C.c_int32)]
+
+
+# include/bdl_rank.h: additive to the ABI, as DIAG_EXPORTS
+RANK_EXPORTS = {
+    "bdl_rank_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
+    "bdl_rank": (C.c_int, [C.POINTER(RankArgs), C.c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -497,7 +522,8 @@ def lib():
                                       + list(PREDICT_EXPORTS.items())
                                       + list(FN_EXPORTS.items())
                                       + list(TEMPER_EXPORTS.items())
-                                      + list(MIXTURE_EXPORTS.items())):
+                                      + list(MIXTURE_EXPORTS.items())
+                                      + list(RANK_EXPORTS.items())):
                 fn = getattr(h, name)
                 fn.restype = res
                 fn.argtypes = argt

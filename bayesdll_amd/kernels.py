@@ -978,6 +978,114 @@ def predict(logits, labels=None, *, groups=1, totals=None, reset=False, num_bins
     return outs, totals
 
 
+def rank_bytes_per_example(counts=False):
+    """Algorithmic HBM bytes per example of one rank call: the
+    score and its mark read, the three counts written to the workspace and read
+    by the finalise with the mark, 12 B more where the count vectors are asked
+    for.  (The O(n^2) count itself re-reads the row from L2 / LDS, not HBM.)"""
+    return 8 + 12 + 12 + 4 + (12 if counts else 0)
+
+
+def rank_summary(row):
+    """One row's host-read bdl_rank_totals as a dict: n_pos (P), n_neg (Nn),
+    n_excluded, u2, fp_at_tpr, ap_sum and auroc = u2 / (2 * P * Nn), ap =
+    ap_sum / P, fpr = fp_at_tpr / Nn — NaN where the denominator is 0 (or no
+    threshold keeps the true positives asked for)."""
+    P, Nn, u2 = int(row["n_pos"]), int(row["n_neg"]), int(row["u2"])
+    fp, aps = int(row["fp_at_tpr"]), float(row["ap_sum"])
+    nan = float("nan")
+    return {"n_pos": P, "n_neg": Nn, "n_excluded": int(row["n_excluded"]), "u2": u2,
+            "fp_at_tpr": fp, "ap_sum": aps,
+            "auroc": u2 / (2 * P * Nn) if P and Nn else nan,
+            "ap": aps / P if P else nan,
+            "fpr": fp / Nn if Nn and fp >= 0 else nan}
+
+
+class RankResult:
+    """What `rank` returns: bdl_rank_totals[rows] in device memory (`buf`) and,
+    with counts=True, the uint32-valued [rows, n] tensors `ge_pos`, `ge_neg`,
+    `gt_neg` (stored as int32: n < 2^31).  `read()` is the one host read (a
+    structured array with the struct's fields), `summary()` the list of
+    rank_summary dicts, one per row."""
+
+    def __init__(self, rows, device, buf=None):
+        self.rows = int(rows)
+        nbytes = self.rows * C.sizeof(L.RankTotals)
+        if buf is None:
+            buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        elif (not torch.is_tensor(buf) or buf.dtype != torch.uint8 or buf.numel() != nbytes
+              or not buf.is_contiguous() or buf.device != device):
+            raise ValueError(f"rank: totals must be a contiguous uint8 tensor of {nbytes} bytes "
+                             "on the scores' device")
+        self.buf = buf
+        self.ge_pos = self.ge_neg = self.gt_neg = None
+
+    def read(self):
+        return np.frombuffer(self.buf.cpu().numpy().tobytes(), dtype=np.dtype(L.RankTotals))
+
+    def summary(self):
+        return [rank_summary(r) for r in self.read()]
+
+
+def rank(scores, marks, *, scores_per_group=1, need=None, tpr=(19, 20), counts=False,
+         totals=None):
+    """Exact rank statistics of score rows against 0 / 1 marks (bdl_rank,
+    include/bdl_rank.h: the definitions): the integer pair counts behind AUROC,
+    average precision and the false-positive rate at a true-positive rate, by
+    counting all pairs — no sort, every integer independent of geometry and
+    order.  scores: fp32, contiguous [rows, n], higher = more positive.  marks:
+    int32, contiguous [rows / scores_per_group, n] (the rows of a group share
+    their marks) or [1, n] / [n] (shared by all rows); 1 positive, 0 negative,
+    anything else — and a NaN score — excludes the example.  need: the true
+    positives fp_at_tpr must keep, for every row; None: ceil(P * tpr[0] /
+    tpr[1]) of each row in integer arithmetic on the device (19 / 20: FPR at
+    95 % TPR).  counts=True keeps the three per-example count vectors.  totals:
+    a uint8 device tensor of rows * 48 bytes to write into (e.g. a slice of one
+    buffer several calls share, read once).  Two launches on the current
+    stream, no host read here: .read() / .summary() of the result is the one."""
+    if not torch.is_tensor(scores) or scores.dim() != 2:
+        raise ValueError("rank: scores must be a [rows, n] tensor")
+    L.require_hip(scores, "scores")
+    if not scores.is_contiguous():
+        raise ValueError("rank: scores must be contiguous")
+    rows, n = int(scores.shape[0]), int(scores.shape[1])
+    spg = int(scores_per_group)
+    if not 1 <= rows <= L.RANK_MAX_ROWS or not 1 <= n <= L.RANK_MAX_N:
+        raise ValueError(f"rank: 1 <= rows <= {L.RANK_MAX_ROWS} and 1 <= n < 2^31 "
+                         f"(got {tuple(scores.shape)})")
+    if spg < 1 or rows % spg:
+        raise ValueError(f"rank: scores_per_group ({spg}) must divide rows ({rows})")
+    dev = scores.device
+    if (not torch.is_tensor(marks) or marks.dtype != torch.int32 or not marks.is_contiguous()
+            or marks.device != dev or marks.dim() not in (1, 2) or int(marks.shape[-1]) != n):
+        raise ValueError("rank: marks must be a contiguous int32 [mark_rows, n] tensor on the "
+                         "scores' device")
+    mrows = 1 if marks.dim() == 1 else int(marks.shape[0])
+    if mrows not in (1, rows // spg):
+        raise ValueError(f"rank: marks has {mrows} rows; rows / scores_per_group "
+                         f"({rows // spg}) or 1")
+    num, den = int(tpr[0]), int(tpr[1])
+    if (need is not None and int(need) < 1) or not 1 <= num <= den < 2 ** 31:
+        raise ValueError("rank: need >= 1 or None, and 1 <= tpr[0] <= tpr[1] < 2^31")
+    need = 0 if need is None else int(need)
+    res = RankResult(rows, dev, totals)
+    nbytes = int(L.lib().bdl_rank_workspace_bytes(rows, n))
+    ws = _scratch(("rank", dev.index, nbytes),
+                  lambda: torch.empty(nbytes, dtype=torch.uint8, device=dev))
+    a = L.RankArgs()
+    a.scores, a.marks = scores.data_ptr(), marks.data_ptr()
+    if counts:
+        for w in ("ge_pos", "ge_neg", "gt_neg"):
+            t = torch.empty((rows, n), dtype=torch.int32, device=dev)
+            setattr(res, w, t)
+            setattr(a, w, t.data_ptr())
+    a.totals, a.workspace = res.buf.data_ptr(), ws.data_ptr()
+    a.n, a.need, a.rows, a.scores_per_group, a.mark_rows = n, need, rows, spg, mrows
+    a.tpr_num, a.tpr_den = num, den
+    L.check(L.lib().bdl_rank(a, L.current_stream_handle(dev)), "bdl_rank")
+    return res
+
+
 def _temper_rows(what, logp, labels, groups, grid_blocks):
     """The checks `temper_fit` and `temper_report` share, worded as predict's;
     returns (G, N, C, grid, workspace)."""

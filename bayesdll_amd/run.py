@@ -143,6 +143,17 @@ def build_parser():
                          "entropy, mutual information (overall, on wrong against other examples) "
                          "and member disagreement from one fused sweep over the members' logits "
                          "(stacked uncertainty()); per chain with --sweep")
+    ap.add_argument("--detect", action="store_true",
+                    help="with --stacked_chains >= 1: at every evaluation, log how the "
+                         "predictive's uncertainty scores (entropy, mutual information, expected "
+                         "entropy, -confidence, disagreement) rank the misclassified test "
+                         "examples: exact AUROC, average precision and FPR at 95 %% TPR from an "
+                         "all-pairs count on the device (stacked detection()); per chain with "
+                         "--sweep")
+    ap.add_argument("--detect_shift", type=float, default=None, metavar="SIGMA",
+                    help="with --detect: also rank a shifted copy of the test split (its inputs "
+                         "plus SIGMA x standard normal noise from a generator seeded by the run's "
+                         "seed; the same examples in the same order) against the test split")
     ap.add_argument("--gmm_weights", action="store_true",
                     help="with --stacked_chains >= 1 and a cyclical method: at every cycle end, "
                          "score max(1, nst) posterior draws of all chains on the training set "
@@ -204,6 +215,39 @@ def check_uncertainty(ap, args):
         ap.error("--uncertainty reports the stacked chains' predictive: it needs "
                  "--stacked_chains >= 1")
     return args.uncertainty
+
+
+def check_detect(ap, args):
+    """--detect needs stacked chains; --detect_shift SIGMA needs --detect and
+    SIGMA > 0 (ap.error otherwise)."""
+    if args.detect and args.stacked_chains < 1:
+        ap.error("--detect ranks the stacked chains' uncertainty scores: it needs "
+                 "--stacked_chains >= 1")
+    if args.detect_shift is not None and not args.detect:
+        ap.error("--detect_shift builds the shifted set of --detect: it needs --detect")
+    if args.detect_shift is not None and not args.detect_shift > 0:
+        ap.error("--detect_shift: SIGMA must be > 0")
+    return args.detect, args.detect_shift
+
+
+class ShiftedLoader:
+    """The batches of `loader` with sigma x N(0, 1) noise added to the inputs,
+    from a generator seeded by `seed` at every pass (the same shifted set every
+    time; the same examples in the same order, the labels passed through)."""
+
+    def __init__(self, loader, sigma, seed):
+        self.loader, self.sigma, self.seed = loader, float(sigma), int(seed)
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        g = None
+        for x, y in self.loader:
+            if g is None:
+                g = torch.Generator(device=x.device).manual_seed(self.seed)
+            yield x + self.sigma * torch.randn(x.shape, device=x.device, dtype=x.dtype,
+                                               generator=g), y
 
 
 def check_gmm_weights(ap, args):
@@ -378,6 +422,7 @@ def main(argv=None):
     check_health(ap, args)
     check_ess(ap, args)
     check_uncertainty(ap, args)
+    check_detect(ap, args)
     check_gmm_weights(ap, args)
     check_temperature_scale(ap, args)
     check_by_tensor(ap, args)
@@ -457,6 +502,8 @@ def main(argv=None):
             kw["fn_batch"] = args.fn_batch
         S = cls(net, args.stacked_chains, args, logger=logger, init="reinit", graph=args.graph,
                 net0=net0, **kw)
+        if args.detect_shift is not None:
+            S.detect_shifted = ShiftedLoader(test_loader, args.detect_shift, args.seed)
         logger.info(f"{args.stacked_chains} stacked chains on this device "
                     f"(chain ids {S.chain0}..{S.chain0 + S.K - 1})")
         hist = S.train(train_loader, test_loader)

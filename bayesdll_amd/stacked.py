@@ -37,6 +37,7 @@ in the forward pass (torch.func returns zeros, not None, for unused inputs).
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 import time
 
@@ -346,6 +347,9 @@ class StackedState:
 def st_big(st):
     """Worth tuning the launch geometry for (small sweeps are launch-bound)."""
     return st.device.type == "cuda" and st.n >= 1 << 20
+
+
+DETECTION_SCORES = ("entropy", "mutual_info", "expected_entropy", "neg_confidence", "disagree")
 
 
 def _single_process(what):
@@ -1614,6 +1618,134 @@ class _StackedSampler:
                 f"{r['mutual_info_correct']:.4f}), disagreement = {r['disagreement']:.4f}; "
                 f"{r['n_nonfinite']} non-finite")
 
+    # ------------------------------------------------------------ detection
+    detect_shifted = None  # run.py --detect_shift: the shifted loader `_report_detection` ranks
+
+    def _detection_outputs(self, loader, G, labelled):
+        """`uncertainty`'s sweep over a loader, keeping the per-example outputs
+        the detection scores are made of on the device: ({output: [G, N]},
+        labels [N] or None, classes, members).  A batch is (x, y) or, where
+        labels are not needed, x alone."""
+        dev = self.args.device
+        want = ("entropy", "expected_entropy", "mutual_info", "confidence", "pred", "disagree")
+        tot, pieces, ys, bufs, classes = None, [], [], {}, 0
+        was = self.net.training
+        self.net.eval()
+        try:
+            for batch in loader:
+                x, y = batch if isinstance(batch, (tuple, list)) else (batch, None)
+                x = x.to(dev)
+                if labelled:
+                    y = y.to(dev).to(torch.int64).contiguous()
+                    ys.append(y)
+                lg = self._member_logits(x, bufs)
+                classes = int(lg.shape[-1])
+                outs, tot = K.predict(lg, y if labelled else None, groups=G, totals=tot,
+                                      want=want)
+                pieces.append(outs)
+        finally:
+            self.net.train(was)
+        if tot is None:
+            raise ValueError("detection: a loader is empty")
+        outs = {w: torch.cat([p[w] for p in pieces], 1) for w in want}
+        return outs, (torch.cat(ys) if labelled else None), classes, tot.members
+
+    @staticmethod
+    def _detection_rows(outs, names):
+        """[G * len(names), N] score rows, the scores of a group adjacent."""
+        make = {"entropy": lambda o: o["entropy"], "mutual_info": lambda o: o["mutual_info"],
+                "expected_entropy": lambda o: o["expected_entropy"],
+                "neg_confidence": lambda o: -o["confidence"],
+                "disagree": lambda o: o["disagree"].float()}
+        s = torch.stack([make[nm](outs) for nm in names], 1)  # [G, S, N]
+        return s.reshape(-1, s.shape[-1]).contiguous()
+
+    def detection(self, loader, shifted=None, *, by_chain=False, scores=None):
+        """How well do the ensemble's uncertainty scores RANK the examples?
+        AUROC, average precision and the false-positive rate at 95 % true
+        positives of every score in `scores` (default DETECTION_SCORES:
+        entropy, mutual_info, expected_entropy, neg_confidence = -confidence,
+        disagree as a float; higher = more suspect) for two tasks.
+        `misclassification`: over `loader`, the positives are the examples the
+        vote gets wrong (pred != label); unlabelled and non-finite examples
+        are excluded.  `shift` (only with `shifted`, a second loader whose
+        labels, if any, are not read): the scores of both loaders concatenated
+        on the device, the examples of `shifted` the positives; only
+        non-finite examples are excluded.  The scores are `uncertainty`'s
+        per-example outputs of `evaluate`'s members, uniformly weighted
+        (`draws` advances as one `uncertainty` call per loader would advance
+        it; with nst > 0 the two loaders are scored by the same mixture in
+        distribution, not by the same draws).  They stay on the device; one
+        kernels.rank call per task counts all pairs exactly (every integer is
+        independent of geometry and order), and ONE host read at the end
+        fetches both tasks' totals.  Returns {task: {score: {auroc, ap, fpr95},
+        n_pos, n_neg, n_excluded}, members}; by_chain=True: every chain's own
+        mixture, every value a list of K.  There is no weights="gmm" and no
+        temperature here: a rank statistic is invariant under a monotone map
+        of the score, but not under a change of the mixture, and the weighted
+        mixture has no per-example outputs.  This process's chains only."""
+        _single_process("detection")
+        names = tuple(DETECTION_SCORES if scores is None else scores)
+        if not names or any(nm not in DETECTION_SCORES for nm in names):
+            raise ValueError(f"detection: scores from {DETECTION_SCORES}")
+        G, S = self.K if by_chain else 1, len(names)
+        outs, y, classes, members = self._detection_outputs(loader, G, True)
+        bad = outs["pred"] < 0  # non-finite: its disagree (-1) is no score
+        lab = (y >= 0) & (y < classes)
+        marks = torch.where(bad | ~lab.unsqueeze(0), 2, outs["pred"].ne(y.unsqueeze(0)).int())
+        tasks = [("misclassification", self._detection_rows(outs, names),
+                  marks.to(torch.int32).contiguous())]
+        if shifted is not None:
+            outs2, _, _, _ = self._detection_outputs(shifted, G, False)
+            both = {w: torch.cat([outs[w], outs2[w]], 1) for w in outs}
+            marks = torch.cat([torch.zeros_like(outs["pred"]), torch.ones_like(outs2["pred"])], 1)
+            marks = torch.where(both["pred"] < 0, 2, marks)
+            tasks.append(("shift", self._detection_rows(both, names),
+                          marks.to(torch.int32).contiguous()))
+        size = G * S * C.sizeof(L.RankTotals)
+        buf = torch.empty(len(tasks) * size, dtype=torch.uint8, device=self.args.device)
+        for i, (_, rows, marks) in enumerate(tasks):
+            K.rank(rows, marks, scores_per_group=S, totals=buf[i * size:(i + 1) * size])
+        host = np.frombuffer(buf.cpu().numpy().tobytes(), dtype=np.dtype(L.RankTotals))  # the read
+        res = {"members": members}
+        for i, (task, _, _) in enumerate(tasks):
+            rows = [K.rank_summary(r) for r in host[i * G * S:(i + 1) * G * S]]
+            d = {}
+            for s, nm in enumerate(names):
+                per = [{"auroc": rows[g * S + s]["auroc"], "ap": rows[g * S + s]["ap"],
+                        "fpr95": rows[g * S + s]["fpr"]} for g in range(G)]
+                d[nm] = {k: [p[k] for p in per] for k in per[0]} if by_chain else per[0]
+            for k in ("n_pos", "n_neg", "n_excluded"):  # the same for every score of a group
+                v = [rows[g * S][k] for g in range(G)]
+                d[k] = v if by_chain else v[0]
+            res[task] = d
+        return res
+
+    def _report_detection(self, ep, rec, loader, log):
+        """One log line per task (one per chain and task under per_chain) and
+        rec["detection"] from `detection()` (run.py --detect, --detect_shift)."""
+        by_chain = self.per_chain is not None
+        try:
+            d = self.detection(loader, self.detect_shifted, by_chain=by_chain)
+        except ValueError as e:
+            log(f"(Epoch {ep}) detection: {e}")
+            return
+        rec["detection"] = d
+        for task in ("misclassification", "shift"):
+            if task not in d:
+                continue
+            for k in range(self.K if by_chain else 1):
+                pick = (lambda v: v[k]) if by_chain else (lambda v: v)
+                who = f"over {self.K} chains"
+                if by_chain:
+                    who = f"chain {self.chain0 + k}: {PC.describe(self.per_chain, self.swept, k)}"
+                t = d[task]
+                parts = [f"{nm}: AUROC = {pick(t[nm]['auroc']):.4f}, AP = {pick(t[nm]['ap']):.4f}, "
+                         f"FPR95 = {pick(t[nm]['fpr95']):.4f}" for nm in DETECTION_SCORES]
+                log(f"(Epoch {ep}) {task} detection {who} ({d['members']} members, "
+                    f"{pick(t['n_pos'])} positives, {pick(t['n_neg'])} negatives, "
+                    f"{pick(t['n_excluded'])} excluded): " + "; ".join(parts))
+
     # ---------------------------------------------------------- checkpoint
     def state_dict(self):
         """Everything an exact continuation of all K chains needs: the stacked
@@ -1691,6 +1823,8 @@ class _StackedSampler:
                     f"error = {rec['test'][1]:.4f}")
                 if getattr(self.args, "uncertainty", False):  # opt-in (run.py --uncertainty)
                     self._report_uncertainty(ep, rec, test_loader, log)
+                if getattr(self.args, "detect", False):  # opt-in (run.py --detect)
+                    self._report_detection(ep, rec, test_loader, log)
                 if self.per_chain is not None:
                     self._report_chains(ep, rec, test_loader, log)
                 if getattr(self.args, "rhat", False):  # opt-in (run.py --rhat)
