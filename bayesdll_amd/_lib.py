@@ -11,6 +11,7 @@ import ctypes as C
 import os
 import threading
 
+import numpy as np
 import torch  # noqa: F401  — load torch's HIP runtime first so the .so binds to it
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -495,6 +496,37 @@ RANK_EXPORTS = {
     "bdl_rank": (C.c_int, [C.POINTER(RankArgs), C.c_void_p]),
 }
 
+DIVERSITY_MAX_VOTERS, DIVERSITY_MAX_CLASSES, DIVERSITY_WAVE_VOTERS = 64, 8192, 16
+DIVERSITY_TILE, DIVERSITY_LDS_STRIDE, DIVERSITY_MAX_GRID = 64, 68, 1024
+DIVERSITY_DEFAULT_WORKSPACE = 32 << 20
+DIVERSITY_RESET = 0x1
+DIVERSITY_INT_MATRICES = ("disagree", "both_wrong", "kl_unbounded")
+DIVERSITY_SUM_MATRICES = ("tv_sum", "kl_sum")
+
+
+def diversity_totals_dtype(voters):
+    """include/bdl_diversity.h: the totals of P voters as one NumPy record —
+    bdl_diversity_header, then the five [P, P] matrices in the header's order."""
+    P = int(voters)
+    return np.dtype([(k, np.int64) for k in ("n", "n_labelled", "n_nonfinite", "voters")]
+                    + [(k, np.int64, (P, P)) for k in DIVERSITY_INT_MATRICES]
+                    + [(k, np.float64, (P, P)) for k in DIVERSITY_SUM_MATRICES])
+
+
+class DiversityArgs(C.Structure):
+    """include/bdl_diversity.h bdl_diversity_args."""
+    _fields_ = [("logits", _fp), ("labels", _fp), ("totals", _fp), ("workspace", _fp),
+                ("batch", C.c_int64), ("voters", C.c_int32), ("classes", C.c_int32),
+                ("grid_blocks", C.c_int32), ("flags", C.c_int32)]
+
+
+# include/bdl_diversity.h: additive to the ABI, as DIAG_EXPORTS
+DIVERSITY_EXPORTS = {
+    "bdl_diversity_totals_bytes": (C.c_int64, [C.c_int32]),
+    "bdl_diversity_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "bdl_diversity": (C.c_int, [C.POINTER(DiversityArgs), C.c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -523,7 +555,8 @@ def lib():
                                       + list(FN_EXPORTS.items())
                                       + list(TEMPER_EXPORTS.items())
                                       + list(MIXTURE_EXPORTS.items())
-                                      + list(RANK_EXPORTS.items())):
+                                      + list(RANK_EXPORTS.items())
+                                      + list(DIVERSITY_EXPORTS.items())):
                 fn = getattr(h, name)
                 fn.restype = res
                 fn.argtypes = argt

@@ -1086,6 +1086,175 @@ def rank(scores, marks, *, scores_per_group=1, need=None, tpr=(19, 20), counts=F
     return res
 
 
+def diversity_bytes_per_example(voters, classes):
+    """Algorithmic HBM bytes per example of one diversity call:
+    every voter's row read once (its two re-reads come from the caches) and the
+    label."""
+    return 4 * int(voters) * int(classes) + 8
+
+
+def diversity_summary(raw):
+    """One host-read totals block of bdl_diversity (a record of
+    _lib.diversity_totals_dtype, or a dict of its fields) as [P, P] NumPy
+    matrices: disagreement (the rate over n), tv (the mean total variation), kl
+    (directed: kl[i, j] is the mean KL(p_i || p_j) over the examples where it is
+    bounded, NaN where there is none), sym_kl = kl + kl.T, kl_unbounded (the
+    counts), double_fault = both_wrong / n_labelled, error_correlation (the phi
+    coefficient of the 2 x 2 table of i wrong against j wrong that both_wrong
+    and its diagonal determine; NaN where a voter is always or never wrong);
+    error [P] (the diagonal of double_fault); n, n_labelled, n_nonfinite.  A
+    mean over nothing is NaN."""
+    n, nl = int(raw["n"]), int(raw["n_labelled"])
+    dis = np.asarray(raw["disagree"], dtype=np.float64)
+    bw = np.asarray(raw["both_wrong"], dtype=np.float64)
+    unb = np.asarray(raw["kl_unbounded"], dtype=np.int64)
+    tv = np.asarray(raw["tv_sum"], dtype=np.float64)
+    kls = np.asarray(raw["kl_sum"], dtype=np.float64)
+    nan = float("nan")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        bounded = n - unb
+        kl = np.where(bounded > 0, kls / np.where(bounded > 0, bounded, 1), nan)
+        e = np.diag(bw)
+        # phi = (N n11 - e_i e_j) / sqrt(e_i (N - e_i) e_j (N - e_j))
+        var = e * (nl - e)
+        den = np.sqrt(np.outer(var, var))
+        phi = np.where(den > 0, (nl * bw - np.outer(e, e)) / np.where(den > 0, den, 1), nan)
+        out = {"disagreement": dis / n if n else np.full_like(dis, nan),
+               "tv": tv / n if n else np.full_like(tv, nan),
+               "kl": kl, "sym_kl": kl + kl.T, "kl_unbounded": unb,
+               "error": e / nl if nl else np.full_like(e, nan),
+               "double_fault": bw / nl if nl else np.full_like(bw, nan),
+               "error_correlation": phi}
+    out.update(n=n, n_labelled=nl, n_nonfinite=int(raw["n_nonfinite"]))
+    return out
+
+
+DIVERSITY_PAIR_KEYS = ("disagreement", "tv", "sym_kl", "double_fault")
+
+
+def diversity_pairs(d):
+    """What a reader of `diversity_summary`'s symmetric matrices asks first: for
+    each of DIVERSITY_PAIR_KEYS the mean over the pairs i < j and the smallest
+    and the largest pair, {"mean", "min", "min_pair", "max", "max_pair"} — the
+    lowest pair in row-major order among equals, NaN entries left out (None / NaN
+    where every pair is NaN) — and `nearest`: for every voter the other voter
+    with the smallest tv to it (the lowest index among equals)."""
+    P = int(np.asarray(d["tv"]).shape[0])
+    out = {}
+    for key in DIVERSITY_PAIR_KEYS:
+        m = np.asarray(d[key], dtype=np.float64)
+        lo = hi = None
+        vals = []
+        for i in range(P):
+            for j in range(i + 1, P):
+                v = float(m[i, j])
+                if v != v:
+                    continue
+                vals.append(v)
+                if lo is None or v < lo[0]:
+                    lo = (v, (i, j))
+                if hi is None or v > hi[0]:
+                    hi = (v, (i, j))
+        nan = float("nan")
+        out[key] = {"mean": float(np.mean(vals)) if vals else nan,
+                    "min": lo[0] if lo else nan, "min_pair": lo[1] if lo else None,
+                    "max": hi[0] if hi else nan, "max_pair": hi[1] if hi else None}
+    tv = np.asarray(d["tv"], dtype=np.float64)
+    nearest = []
+    for i in range(P):
+        row = [(tv[i, j] if tv[i, j] == tv[i, j] else np.inf, j) for j in range(P) if j != i]
+        nearest.append(min(row)[1])
+    out["nearest"] = nearest
+    return out
+
+
+class DiversityTotals:
+    """The running totals of `diversity` calls: the header and the five [P, P]
+    matrices of include/bdl_diversity.h in device memory.  `read()` is the one
+    host read (a record of _lib.diversity_totals_dtype(P)), `summary()` the
+    dict of diversity_summary."""
+
+    def __init__(self, voters, device):
+        self.voters = int(voters)
+        self.buf = torch.empty(L.diversity_totals_dtype(self.voters).itemsize, dtype=torch.uint8,
+                               device=device)
+        self.fresh = True  # nothing accumulated: the first call resets
+
+    def read(self):
+        if self.fresh:
+            raise ValueError("diversity: these totals hold nothing yet")
+        return np.frombuffer(self.buf.cpu().numpy().tobytes(),
+                             dtype=L.diversity_totals_dtype(self.voters))[0]
+
+    def summary(self):
+        return diversity_summary(self.read())
+
+
+def diversity_default_grid(voters, batch, classes, device):
+    """The grid bdl_diversity launches with grid_blocks = 0: one workgroup per
+    team-load of examples, at most two per CU, within the workspace bound."""
+    P = int(voters)
+    wave = P <= L.DIVERSITY_WAVE_VOTERS and int(classes) <= L.DIVERSITY_TILE
+    trips = -(-int(batch) // (4 if wave else 1))
+    part = (L.diversity_totals_dtype(P).itemsize + 15) // 16 * 16
+    cap = max(1, min(L.DIVERSITY_DEFAULT_WORKSPACE // part, L.DIVERSITY_MAX_GRID))
+    cus = torch.cuda.get_device_properties(device).multi_processor_count
+    return max(1, min(trips, 2 * cus, cap))
+
+
+def diversity(logits, labels=None, *, totals=None, reset=False, grid_blocks=0):
+    """Pairwise diversity of an ensemble's voters in one fused sweep
+    (bdl_diversity, include/bdl_diversity.h: the definitions and the arithmetic
+    contract): per ordered pair (i, j) the count of examples on which the votes
+    differ, on which both are wrong, the summed total variation and KL(p_i ||
+    p_j) between the voters' softmaxes, and how often that KL is infinite.
+    logits: fp32, contiguous [P, B, C], 2 <= P <= 64 (a log-probability row is
+    a valid logit row).  labels: int64 [B] on the device or None; a label
+    outside [0, C) leaves the example unlabelled.  Returns the DiversityTotals
+    handle the call ADDED to (a new one, or the one passed in; reset=True
+    overwrites it).  Two launches on the current stream, no host read here:
+    totals.read() / .summary() is the one."""
+    if not torch.is_tensor(logits) or logits.dim() != 3:
+        raise ValueError("diversity: logits must be a [P, B, C] tensor")
+    L.require_hip(logits, "logits")
+    if not logits.is_contiguous():
+        raise ValueError("diversity: logits must be contiguous")
+    P, B, Cn = (int(v) for v in logits.shape)
+    if not 2 <= P <= L.DIVERSITY_MAX_VOTERS:
+        raise ValueError(f"diversity: 2 <= voters <= {L.DIVERSITY_MAX_VOTERS} (got {P})")
+    if B < 1 or not 1 <= Cn <= L.DIVERSITY_MAX_CLASSES:
+        raise ValueError(f"diversity: batch >= 1 and 1 <= classes <= {L.DIVERSITY_MAX_CLASSES} "
+                         f"(got {tuple(logits.shape)})")
+    grid = int(grid_blocks)
+    if not 0 <= grid <= L.DIVERSITY_MAX_GRID:
+        raise ValueError(f"diversity: grid_blocks in [0, {L.DIVERSITY_MAX_GRID}]")
+    dev = logits.device
+    if labels is not None:
+        if (not torch.is_tensor(labels) or labels.dtype != torch.int64 or labels.shape != (B,)
+                or not labels.is_contiguous() or labels.device != dev):
+            raise ValueError("diversity: labels must be a contiguous int64 [B] tensor on the "
+                             "logits' device")
+    if totals is None:
+        totals = DiversityTotals(P, dev)
+    elif totals.voters != P or totals.buf.device != dev:
+        raise ValueError("diversity: these totals were started with other voters or on another "
+                         "device")
+    if grid == 0:  # the library's default, so that the workspace is sized for it
+        grid = diversity_default_grid(P, B, Cn, dev)
+    nbytes = int(L.lib().bdl_diversity_workspace_bytes(P, grid))
+    ws = _scratch(("diversity", dev.index, nbytes),
+                  lambda: torch.empty(nbytes, dtype=torch.uint8, device=dev))
+    a = L.DiversityArgs()
+    a.logits = logits.data_ptr()
+    a.labels = None if labels is None else labels.data_ptr()
+    a.totals, a.workspace = totals.buf.data_ptr(), ws.data_ptr()
+    a.batch, a.voters, a.classes, a.grid_blocks = B, P, Cn, grid
+    a.flags = L.DIVERSITY_RESET if (reset or totals.fresh) else 0
+    L.check(L.lib().bdl_diversity(a, L.current_stream_handle(dev)), "bdl_diversity")
+    totals.fresh = False
+    return totals
+
+
 def _temper_rows(what, logp, labels, groups, grid_blocks):
     """The checks `temper_fit` and `temper_report` share, worded as predict's;
     returns (G, N, C, grid, workspace)."""

@@ -154,6 +154,13 @@ def build_parser():
                     help="with --detect: also rank a shifted copy of the test split (its inputs "
                          "plus SIGMA x standard normal noise from a generator seeded by the run's "
                          "seed; the same examples in the same order) against the test split")
+    ap.add_argument("--diversity", action="store_true",
+                    help="with --stacked_chains >= 2: at every evaluation, log which chains "
+                         "predict the same function: the mean pairwise disagreement of the "
+                         "chains' own predictives with its closest and furthest pair, the mean "
+                         "total variation, symmetric KL and double fault, from one fused sweep "
+                         "per batch (stacked diversity()); the K x K matrices go to the epoch "
+                         "record; works with --sweep")
     ap.add_argument("--gmm_weights", action="store_true",
                     help="with --stacked_chains >= 1 and a cyclical method: at every cycle end, "
                          "score max(1, nst) posterior draws of all chains on the training set "
@@ -228,6 +235,14 @@ def check_detect(ap, args):
     if args.detect_shift is not None and not args.detect_shift > 0:
         ap.error("--detect_shift: SIGMA must be > 0")
     return args.detect, args.detect_shift
+
+
+def check_diversity(ap, args):
+    """--diversity compares stacked chains pairwise (ap.error otherwise)."""
+    if args.diversity and args.stacked_chains < 2:
+        ap.error("--diversity compares the stacked chains pairwise: it needs "
+                 "--stacked_chains >= 2")
+    return args.diversity
 
 
 class ShiftedLoader:
@@ -423,6 +438,7 @@ def main(argv=None):
     check_ess(ap, args)
     check_uncertainty(ap, args)
     check_detect(ap, args)
+    check_diversity(ap, args)
     check_gmm_weights(ap, args)
     check_temperature_scale(ap, args)
     check_by_tensor(ap, args)

@@ -1746,6 +1746,71 @@ class _StackedSampler:
                     f"{pick(t['n_pos'])} positives, {pick(t['n_neg'])} negatives, "
                     f"{pick(t['n_excluded'])} excluded): " + "; ".join(parts))
 
+    # ------------------------------------------------------------ diversity
+    def diversity(self, loader):
+        """WHICH chains predict the same function?  The pairwise view of the K
+        chains over a data loader (the network in eval mode, as `evaluate`):
+        [K, K] NumPy matrices `disagreement` (the share of examples on which
+        two chains vote differently), `tv` (the mean total variation between
+        their predictive distributions), `kl` (directed, kl[i, j] the mean
+        KL(chain i || chain j) over the examples where it is finite) with
+        `sym_kl` and the `kl_unbounded` counts, `double_fault` (both wrong),
+        `error_correlation` (phi of the two chains' errors), `error` [K], and
+        n, n_labelled, n_nonfinite (kernels.diversity_summary) — plus `summary`
+        (kernels.diversity_pairs): the mean, closest and furthest pair of
+        disagreement, tv, sym_kl and double_fault, and `nearest[i]`, the chain
+        with the smallest tv to chain i.  A voter is a chain's OWN predictive:
+        the uniform mixture of that chain's collected components x nst draws
+        (`chain_logprob`'s members, the same Philox keys; `draws` advances as
+        an `evaluate` over the loader would advance it), the chain's current
+        theta while nothing is collected.  Per batch one kernels.predict sweep
+        (groups = K) leaves the K log mixtures on the device and one
+        kernels.diversity sweep adds their pair totals there; ONE host read at
+        the end.  Works under per_chain (the voters are then different models).
+        This process's chains only; K >= 2."""
+        _single_process("diversity")
+        if self.K < 2:
+            raise ValueError("diversity: compares the stacked chains pairwise: it needs K >= 2 "
+                             f"(got {self.K})")
+        dev = self.args.device
+        ptot, tot, bufs = None, None, {}
+        was = self.net.training
+        self.net.eval()
+        try:
+            for x, y in loader:
+                x, y = x.to(dev), y.to(dev).to(torch.int64).contiguous()
+                lg = self._member_logits(x, bufs)
+                outs, ptot = K.predict(lg, y, groups=self.K, totals=ptot, want=("logp",))
+                tot = K.diversity(outs["logp"], y, totals=tot)
+        finally:
+            self.net.train(was)
+        if tot is None:
+            raise ValueError("diversity: the loader is empty")
+        res = tot.summary()  # the one host read
+        res["summary"] = K.diversity_pairs(res)
+        return res
+
+    def _report_diversity(self, ep, rec, loader, log):
+        """One [Diversity] log line and rec["diversity"] (the matrices as
+        lists) from `diversity()` (run.py --diversity)."""
+        try:
+            d = self.diversity(loader)
+        except ValueError as e:
+            log(f"(Epoch {ep}) [Diversity] {e}")
+            return
+        rec["diversity"] = {k: (v.tolist() if isinstance(v, np.ndarray) else v)
+                            for k, v in d.items()}
+        s = d["summary"]
+
+        def pair(p):
+            return "none" if p is None else f"chains {self.chain0 + p[0]} and {self.chain0 + p[1]}"
+        dis = s["disagreement"]
+        log(f"(Epoch {ep}) [Diversity] {self.K} chains, {d['n']} examples: disagreement = "
+            f"{dis['mean']:.4f} (closest {pair(dis['min_pair'])}: {dis['min']:.4f}, furthest "
+            f"{pair(dis['max_pair'])}: {dis['max']:.4f}), tv = {s['tv']['mean']:.4f}, sym_kl = "
+            f"{s['sym_kl']['mean']:.4f}, double_fault = {s['double_fault']['mean']:.4f}; "
+            f"{d['n_nonfinite']} non-finite")
+
     # ---------------------------------------------------------- checkpoint
     def state_dict(self):
         """Everything an exact continuation of all K chains needs: the stacked
@@ -1825,6 +1890,8 @@ class _StackedSampler:
                     self._report_uncertainty(ep, rec, test_loader, log)
                 if getattr(self.args, "detect", False):  # opt-in (run.py --detect)
                     self._report_detection(ep, rec, test_loader, log)
+                if getattr(self.args, "diversity", False):  # opt-in (run.py --diversity)
+                    self._report_diversity(ep, rec, test_loader, log)
                 if self.per_chain is not None:
                     self._report_chains(ep, rec, test_loader, log)
                 if getattr(self.args, "rhat", False):  # opt-in (run.py --rhat)
