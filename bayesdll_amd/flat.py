@@ -219,17 +219,22 @@ class FlatState:
         # reference skips a parameter whose .grad is None after net.zero_grad()
         # + backward (`if p.grad is not None`, e.g. methods/csghmc.py:749).
         # "tensor" mode sees it directly (.grad stays None); "flat" mode marks
-        # it with a post-accumulate hook (its .grad views always exist).
+        # it with a gradient hook (its .grad views always exist).  The hook
+        # sees the gradient itself: autograd also runs a parameter's hooks
+        # when a backward function returned None for it (an undefined
+        # gradient, nothing accumulated) — the reference's .grad stays None
+        # then, so that is no gradient here either.
         self._touched = [False] * len(self.params) if self.grad_mode == "flat" else []
-        self._hooks = [p.register_post_accumulate_grad_hook(self._mark(i))
+        self._hooks = [p.register_hook(self._mark(i))
                        for i, p in enumerate(self.params) if p.requires_grad] \
             if self.grad_mode == "flat" else []
 
     def _mark(self, i):
         touched = self._touched
 
-        def hook(_p):
-            touched[i] = True
+        def hook(grad):
+            if grad is not None:
+                touched[i] = True
         return hook
 
     @classmethod

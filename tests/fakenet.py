@@ -56,15 +56,21 @@ class _PrescribedGrad(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        return (None, None, *[g.clone() for g in ctx.grads])
+        return (None, None, *[None if g is None else g.clone() for g in ctx.grads])
 
 
 class FakeNet(nn.Module):
-    """nn.Module whose named_parameters() follow `segments` in order."""
+    """nn.Module whose named_parameters() follow `segments` in order.
+
+    frozen: names of parameters built with requires_grad=False.  no_grad:
+    step -> names of the parameters whose backward returns None in that
+    training step (their .grad stays None after zero_grad + backward, as for a
+    branch the forward pass did not take).  Both default to nothing."""
 
     def __init__(self, segments=TOY_SEGMENTS, readout_name=TOY_READOUT, grad_seed=1234,
-                 grad_scale=0.5, init=None, grad_table=None):
+                 grad_scale=0.5, init=None, grad_table=None, frozen=(), no_grad=None):
         super().__init__()
+        self.no_grad = no_grad
         self.readout_name = readout_name
         self._segments = list(segments)
         for name, shape in self._segments:
@@ -74,7 +80,8 @@ class FakeNet(nn.Module):
                 if not hasattr(mod, part):
                     mod.add_module(part, nn.Module())
                 mod = getattr(mod, part)
-            mod.register_parameter(parts[-1], nn.Parameter(torch.zeros(shape, dtype=torch.float32)))
+            mod.register_parameter(parts[-1], nn.Parameter(torch.zeros(shape, dtype=torch.float32),
+                                                           requires_grad=name not in frozen))
         self.grad_seed = grad_seed
         self.grad_scale = grad_scale
         # optional precomputed grads_for_step vectors (index = step), e.g. on the device
@@ -101,11 +108,12 @@ class FakeNet(nn.Module):
             else:
                 g = grads_for_step(self.grad_seed, self.step, self.n, self.grad_scale)
                 gt = torch.from_numpy(g).to(params[0].device)
+            skip = () if self.no_grad is None else self.no_grad(self.step)
             self.step += 1
             grads, off = [], 0
-            for p in params:
+            for (name, _), p in zip(self._segments, params):
                 k = p.numel()
-                grads.append(gt[off:off + k].view_as(p))
+                grads.append(None if name in skip else gt[off:off + k].view_as(p))
                 off += k
         else:
             grads = [torch.zeros_like(p) for p in params]
