@@ -527,6 +527,19 @@ DIVERSITY_EXPORTS = {
     "bdl_diversity": (C.c_int, [C.POINTER(DiversityArgs), C.c_void_p]),
 }
 
+ORDER_SPANS, ORDER_GRID_STRIDE, ORDER_DYNAMIC = 0, 1, 2
+CLAIM_GROUPS, CLAIM_SLOTS, CLAIM_SLOTS_PER_STREAM = 2048, 16, 4
+DRIFT_EVERY, DRIFT_SAMPLES = 16, 64
+DRIFT_WORDS = 4 + 2 * DRIFT_SAMPLES
+
+# include/bdl_order.h: additive to the ABI, as DIAG_EXPORTS
+ORDER_EXPORTS = {
+    "bdl_order_last": (C.c_int, [C.POINTER(C.c_int32)]),
+    "bdl_order_counters": (C.c_int, [C.c_int32, C.POINTER(C.c_uint32)]),
+    "bdl_sweep_drift": (C.c_int, [C.POINTER(StepArgs), C.c_int32, C.c_void_p, C.c_int64,
+                                  C.POINTER(C.c_int32), C.c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -556,7 +569,8 @@ def lib():
                                       + list(TEMPER_EXPORTS.items())
                                       + list(MIXTURE_EXPORTS.items())
                                       + list(RANK_EXPORTS.items())
-                                      + list(DIVERSITY_EXPORTS.items())):
+                                      + list(DIVERSITY_EXPORTS.items())
+                                      + list(ORDER_EXPORTS.items())):
                 fn = getattr(h, name)
                 fn.restype = res
                 fn.argtypes = argt

@@ -34,6 +34,7 @@
 // validation, launch geometry, the clip-norm / moments / sample kernels).
 #include <algorithm>
 #include "bdl_chain_common.hpp"
+#include "bdl_claim_ring.hpp"
 #include "bdl_measure.h"
 
 #include <mutex>
@@ -50,7 +51,9 @@ thread_local std::string g_last_error;
 // profiles/round1/kernel_v1/sweep_*.log); the Python side autotunes per method.
 int g_blocks_per_cu = 2;
 int g_unroll = 1;
-int g_grid_stride = 1;  // 0: one contiguous span per block; 1: grid-stride sweep
+// 0: one contiguous span per block; 1: grid-stride sweep; 2: claim blocks taken
+// from a device counter (the cSGHMC sweeps; every other launch runs 1)
+int g_grid_stride = 1;
 
 int device_cu_count() {
   static int cached[64] = {0};
@@ -551,7 +554,60 @@ std::vector<const void*> g_captured_funcs;  // step kernels launched into a capt
 thread_local hipGraphExec_t g_redirect_exec = nullptr;
 thread_local hipGraphNode_t g_redirect_node = nullptr;
 
-int launch_step(const bdl_step_args* s, const float* clip, hipStream_t stream, bool bare = false) {
+// The dynamic order's counters (include/bdl_order.h): per device, one
+// allocation of BDL_CLAIM_SLOTS {claim, done} pairs, a pair per 128-B line,
+// zeroed once; bdl_claim_ring.hpp says which pair a launch gets.
+constexpr int kClaimStride = 32;  // uint32 words between two pairs
+struct DeviceClaims {
+  uint32_t* base = nullptr;
+  ClaimRing ring{};
+};
+std::mutex g_claim_mu;
+DeviceClaims g_claims[64];
+thread_local int g_last_order = -1, g_last_slot = -1;
+
+// The pair of the next dynamic-order launch on `stream` (current device), or
+// null: the launch runs order 1.
+uint32_t* claim_pair(hipStream_t stream, int* slot) {
+  bool capturing = false;
+  if (stream) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    capturing = hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+    (void)hipGetLastError();
+  }
+  const bool redirect = g_redirect_exec != nullptr;
+  int dev = 0;
+  if (capturing || redirect || hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
+    return nullptr;
+  std::lock_guard<std::mutex> lk(g_claim_mu);
+  DeviceClaims& d = g_claims[dev];
+  if (!d.base) {
+    const size_t bytes = (size_t)BDL_CLAIM_SLOTS * kClaimStride * sizeof(uint32_t);
+    uint32_t* p = nullptr;
+    if (hipMalloc((void**)&p, bytes) != hipSuccess || hipMemset(p, 0, bytes) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess) {
+      (void)hipGetLastError();
+      if (p) (void)hipFree(p);
+      return nullptr;
+    }
+    d.base = p;
+  }
+  const int sl = claim_ring_next(d.ring, (uintptr_t)stream, capturing, redirect);
+  if (sl < 0) return nullptr;
+  *slot = sl;
+  return d.base + (size_t)sl * kClaimStride;
+}
+
+// bdl_sweep_drift's request: the explore sweep under the drift probe
+struct DriftReq {
+  int order;
+  uint64_t* records;
+  int64_t record_bytes;
+  int32_t* grid;
+};
+
+int launch_step(const bdl_step_args* s, const float* clip, hipStream_t stream, bool bare = false,
+                const DriftReq* drift = nullptr) {
   if (!s) return fail(BDL_ERR_NULL, "bdl_sgmcmc_step: null args");
   if (s->n < 0) return fail(BDL_ERR_ARG, "bdl_sgmcmc_step: n < 0");
   if (s->method < BDL_CSGHMC || s->method > BDL_SGLD_GRAD)
@@ -608,7 +664,8 @@ int launch_step(const bdl_step_args* s, const float* clip, hipStream_t stream, b
   a.nruns = s->nruns;
   a.flags = s->flags;
   a.n = s->n;
-  a.groups_per_block = g_grid_stride ? 0 : iters_per_block * per_iter;
+  const int order = drift ? drift->order : g_grid_stride;
+  a.groups_per_block = order ? 0 : iters_per_block * per_iter;
   a.lr0 = s->lr[0];
   a.lr1 = s->lr[1];
   a.ns0 = s->noise_scale[0];
@@ -631,6 +688,34 @@ int launch_step(const bdl_step_args* s, const float* clip, hipStream_t stream, b
   a.inv_nd = recip_or(s->inv_n_data, s->n_data);
   a.inv_ca = recip_or(s->inv_collect_a, s->collect_a);
   a.inv_cb = recip_or(s->inv_collect_b, s->collect_b);
+
+  // The dynamic order: a cSGHMC launch that gets a counter pair (never one
+  // into a capture or a graph node, claim_pair) and whose run table leaves
+  // room for the claim's LDS words; claim blocks of BDL_CLAIM_GROUPS groups.
+  int slot = -1;
+  uint32_t* pair = nullptr;
+  if (order == 2 && s->method == BDL_CSGHMC &&
+      run_lds_bytes(s) + 16 <= (size_t)kMaxRuns * sizeof(bdl_run))
+    pair = claim_pair(stream, &slot);
+  g_last_order = pair ? 2 : (order ? 1 : 0);
+  g_last_slot = slot;
+  const int32_t citers = (int32_t)(BDL_CLAIM_GROUPS / per_iter);
+  if (pair) grid = capped_grid((iters + citers - 1) / citers, cap);
+  if (drift) {
+    if (order == 2 && !pair)
+      return fail(BDL_ERR_ARG, "bdl_sweep_drift: no counter pair for the dynamic order here");
+    if (drift->record_bytes < grid * (int64_t)(BDL_DRIFT_WORDS * sizeof(uint64_t)))
+      return fail(BDL_ERR_ARG, "bdl_sweep_drift: records too small for the launch's workgroups");
+    *drift->grid = (int32_t)grid;
+    hipLaunchKernelGGL(pick_drift(unroll, pair != nullptr), dim3((unsigned)grid), dim3(kBlock),
+                       run_lds_bytes(s), stream, a, pair, citers, drift->records);
+    return launched("bdl_sweep_drift");
+  }
+  if (pair) {
+    hipLaunchKernelGGL(pick_step_csghmc_dyn(s->noise_mode, s->collect, unroll, bare),
+                       dim3((unsigned)grid), dim3(kBlock), run_lds_bytes(s), stream, a, pair, citers);
+    return launched("bdl_sgmcmc_step");
+  }
 
   if (g_redirect_exec) {
     // the node must be a kernel node running this very kernel (checked on
@@ -894,8 +979,54 @@ int bdl_set_launch_config(int32_t blocks_per_cu, int32_t unroll, int32_t grid_st
   const int prev = (g_grid_stride << 24) | (g_blocks_per_cu << 8) | g_unroll;
   g_blocks_per_cu = blocks_per_cu > 0 ? blocks_per_cu : 2;
   g_unroll = (unroll == 1 || unroll == 2 || unroll == 4) ? unroll : 1;
-  g_grid_stride = grid_stride > 0 ? 1 : 0;
+  g_grid_stride = grid_stride == 2 ? 2 : (grid_stride > 0 ? 1 : 0);  // bdl_order.h: the orders
   return prev;
+}
+
+int bdl_order_last(int32_t* slot) {
+  if (slot) *slot = g_last_slot;
+  return g_last_order;
+}
+
+int bdl_order_counters(int32_t device, uint32_t* out) {
+  if (!out) return fail(BDL_ERR_NULL, "bdl_order_counters: null out");
+  if (device < 0 || device >= 64) return fail(BDL_ERR_ARG, "bdl_order_counters: bad device");
+  std::fill(out, out + 2 * BDL_CLAIM_SLOTS, 0u);
+  std::lock_guard<std::mutex> lk(g_claim_mu);
+  const uint32_t* base = g_claims[device].base;
+  if (!base) return BDL_OK;
+  int cur = 0;
+  uint32_t host[BDL_CLAIM_SLOTS * kClaimStride];
+  if (hipGetDevice(&cur) != hipSuccess || hipSetDevice(device) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(BDL_ERR_LAUNCH, "bdl_order_counters: cannot select the device");
+  }
+  const bool ok = hipDeviceSynchronize() == hipSuccess &&
+                  hipMemcpy(host, base, sizeof(host), hipMemcpyDeviceToHost) == hipSuccess;
+  (void)hipSetDevice(cur);
+  if (!ok) {
+    (void)hipGetLastError();
+    return fail(BDL_ERR_LAUNCH, "bdl_order_counters: reading the counters failed");
+  }
+  for (int i = 0; i < BDL_CLAIM_SLOTS; ++i) {
+    out[2 * i] = host[i * kClaimStride];
+    out[2 * i + 1] = host[i * kClaimStride + 1];
+  }
+  return BDL_OK;
+}
+
+int bdl_sweep_drift(const bdl_step_args* s, int32_t order, uint64_t* records, int64_t record_bytes,
+                    int32_t* grid, void* stream) {
+  if (const int rc = no_redirect("bdl_sweep_drift")) return rc;
+  if (!s || !records || !grid) return fail(BDL_ERR_NULL, "bdl_sweep_drift: null argument");
+  if (s->method != BDL_CSGHMC || s->noise_mode != BDL_NOISE_NONE || s->collect != BDL_COLLECT_NONE)
+    return fail(BDL_ERR_ARG, "bdl_sweep_drift: the probe runs the cSGHMC explore sweep only "
+                "(no noise, no collect)");
+  if (order < 0 || order > 2) return fail(BDL_ERR_ARG, "bdl_sweep_drift: order must be 0, 1 or 2");
+  if (misaligned(records, 7)) return fail(BDL_ERR_ALIGN, "bdl_sweep_drift: records not 8-B aligned");
+  if (s->n == 0) return fail(BDL_ERR_ARG, "bdl_sweep_drift: n == 0");
+  const DriftReq req{order, records, record_bytes, grid};
+  return launch_step(s, nullptr, (hipStream_t)stream, false, &req);
 }
 
 int bdl_build_runs(const bdl_segment* segs, int32_t nseg, int64_t n, bdl_run* out, int32_t max_runs) {

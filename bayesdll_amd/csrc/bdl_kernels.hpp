@@ -11,6 +11,7 @@
 #include <string>
 
 #include "bdl_sgmcmc.h"
+#include "bdl_order.h"
 
 namespace bdl {
 
@@ -971,6 +972,182 @@ __global__ __launch_bounds__(kBlock) void bdl_step_kernel(const KArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// The dynamic sweep order of the cSGHMC sweeps (bdl_set_launch_config order 2,
+// include/bdl_order.h): the vector is cut into claim blocks of `citers`
+// consecutive block iterations; a workgroup takes block blockIdx.x first (no
+// atomic: the launch ramps up as the grid-stride sweep does) and then claims
+// ascending blocks from one device counter, so the work in flight is always
+// the most recently claimed blocks and no workgroup idles while another still
+// has a static share to finish.  One lane issues the claim for the next block
+// before the workgroup streams the current one (its latency sits under a
+// block's worth of traffic); the value reaches the other waves through LDS,
+// double-buffered, one barrier per claim.  claim[0] is the claim counter,
+// claim[1] counts finished workgroups: the last one stores zeros to both, so
+// the pair is ready for its next launch without a memset.
+//
+// These kernels are instances of their own (bdl_step_dyn_kernel): the static
+// orders' kernels (step_body) are not touched by this path.  DYN = false is
+// the static assignment in the same loop, for the drift probe alone.
+// ---------------------------------------------------------------------------
+struct NoProbe {
+  __device__ __forceinline__ void begin() {}
+  __device__ __forceinline__ void tick(int64_t) {}
+  __device__ __forceinline__ void end() {}
+};
+
+// Per-workgroup record of the drift probe (bdl_sweep_drift), BDL_DRIFT_WORDS
+// 64-bit words: [0] wall clock at the first load, [1] after the last store,
+// [2] samples taken, [3] iterations run, then (wall clock, global iteration
+// index) at every BDL_DRIFT_EVERY-th iteration of the workgroup.
+struct DriftProbe {
+  uint64_t* __restrict__ rec;
+  uint32_t it;
+  __device__ __forceinline__ void begin() {
+    if (threadIdx.x == 0) rec[0] = wall_clock64();
+  }
+  __device__ __forceinline__ void tick(int64_t iter) {
+    if (it % BDL_DRIFT_EVERY == 0) {
+      const uint32_t s = it / BDL_DRIFT_EVERY;
+      if (s < BDL_DRIFT_SAMPLES && threadIdx.x == 0) {
+        rec[4 + 2 * s] = wall_clock64();
+        rec[5 + 2 * s] = (uint64_t)iter;
+      }
+    }
+    ++it;
+  }
+  __device__ __forceinline__ void end() {
+    __threadfence();  // this wave's stores have left
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      rec[1] = wall_clock64();
+      rec[2] = min((it + BDL_DRIFT_EVERY - 1) / BDL_DRIFT_EVERY, (uint32_t)BDL_DRIFT_SAMPLES);
+      rec[3] = it;
+    }
+  }
+};
+
+template <int METHOD, int NOISE, int COLLECT, bool RECIP, int UNROLL, bool DYN, class PROBE>
+__device__ __forceinline__ void csg_sweep(const KArgs& a, uint32_t* __restrict__ claim,
+                                          int32_t citers, PROBE probe) {
+  static_assert(is_csghmc_sweep<METHOD>(), "the dynamic order exists for the cSGHMC sweeps");
+  __shared__ uint32_t s_claim[2];
+  const StepConst c = make_step_const<METHOD, COLLECT, kVarRuntime>(a);
+  const int64_t ngroups = (a.n + 3) >> 2;
+  const int64_t nfull = a.n >> 2;
+  constexpr int64_t kIter = (int64_t)kBlock * UNROLL;
+  const int64_t cgroups = (int64_t)citers * kIter;  // groups per claim block
+  int64_t g0, g1, gstep;
+  if constexpr (DYN) {
+    g0 = (int64_t)blockIdx.x * cgroups;
+    g1 = min(g0 + cgroups, ngroups);
+    gstep = kIter;
+  } else if (a.groups_per_block > 0) {
+    g0 = (int64_t)blockIdx.x * a.groups_per_block;
+    g1 = min(g0 + a.groups_per_block, ngroups);
+    gstep = kIter;
+  } else {
+    g0 = (int64_t)blockIdx.x * kIter;
+    g1 = ngroups;
+    gstep = (int64_t)gridDim.x * kIter;
+  }
+  stage_runs(a);
+  probe.begin();
+  uint32_t bad = 0, nxt = 0;
+  int r = -1, par = 0;
+  while (g0 < g1) {
+    if constexpr (DYN) {
+      // the next block's claim, in flight under this block's streaming
+      if (threadIdx.x == 0) nxt = gridDim.x + atomicAdd(claim, 1u);
+    }
+    // claims ascend per workgroup: the run cursor only moves forward
+    if (r < 0) r = find_run_lds(a.nruns, g0 * 4);
+    if constexpr (COLLECT != BDL_COLLECT_NONE && !csg_collect_per_run<COLLECT, UNROLL>()) {
+      for (int64_t gb = g0; gb < g1; gb += gstep) {
+        while (r < a.nruns - 1 && run_end(r) <= gb * 4) ++r;
+        const int64_t gend = min(gb + kIter, g1);
+        const uint32_t attr = run_attr(r);
+        const bool full = gend == gb + kIter && gend <= nfull;
+        if (full && run_end(r) >= gend * 4 && !(attr & kNoFastPath))
+          chunk_fast_dispatch<METHOD, NOISE, COLLECT, RECIP, UNROLL>(a, c, gb, attr,
+                                                                      run_grad(a, r), bad);
+        else if (full && multi_run_ok(a.nruns, r, gend * 4))
+          chunk_multi<METHOD, NOISE, COLLECT, RECIP, UNROLL>(a, c, gb, r, bad);
+        else
+          chunk_slow<METHOD, NOISE, COLLECT, RECIP, UNROLL>(a, c, gb, gend, r, bad);
+        probe.tick(gb / kIter);
+      }
+    } else {
+      for (int64_t gb = g0; gb < g1;) {
+        while (r < a.nruns - 1 && run_end(r) <= gb * 4) ++r;
+        const uint32_t attr = run_attr(r);
+        const int64_t lim = min(min(run_end(r) >> 2, nfull), g1);
+        if (!(attr & kNoFastPath) && gb + kIter <= lim) {
+          const bool head = (attr & BDL_ATTR_HEAD) != 0;
+          const float eta = head ? a.lr1 : a.lr0, ns = head ? a.ns1 : a.ns0;
+          float* gp = run_grad(a, r);
+          do {  // fast_run, with the probe's tick
+            chunk_fast<METHOD, NOISE, COLLECT, RECIP, UNROLL, false, false>(a, c, gb, eta, ns, gp,
+                                                                            bad);
+            probe.tick(gb / kIter);
+            gb += gstep;
+          } while (gb + kIter <= lim);
+          continue;
+        }
+        const int64_t gend = min(gb + kIter, g1);
+        if (gend == gb + kIter && gend <= nfull && multi_run_ok(a.nruns, r, gend * 4))
+          chunk_multi<METHOD, NOISE, COLLECT, RECIP, UNROLL>(a, c, gb, r, bad);
+        else
+          chunk_slow<METHOD, NOISE, COLLECT, RECIP, UNROLL>(a, c, gb, gend, r, bad);
+        probe.tick(gb / kIter);
+        gb += gstep;
+      }
+    }
+    if constexpr (!DYN) {
+      break;
+    } else {
+      if (threadIdx.x == 0) s_claim[par] = nxt;
+      __syncthreads();
+      const uint32_t blk = s_claim[par];
+      par ^= 1;
+      g0 = (int64_t)blk * cgroups;  // past the vector's end: nothing left to claim
+      g1 = min(g0 + cgroups, ngroups);
+    }
+  }
+  report_nonfinite(a, bad);
+  probe.end();
+  if constexpr (DYN) {
+    // every claim of this workgroup has returned (its value ended the loop)
+    if (threadIdx.x == 0 && atomicAdd(claim + 1, 1u) == gridDim.x - 1) {
+      __hip_atomic_store(claim, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(claim + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+template <int METHOD, int NOISE, int COLLECT, int UNROLL>
+__global__ __launch_bounds__(kBlock) void bdl_step_dyn_kernel(const KArgs a, uint32_t* claim,
+                                                              int32_t citers) {
+  if (a.flags & BDL_FLAG_RECIP_DIV)
+    csg_sweep<METHOD, NOISE, COLLECT, true, UNROLL, true, NoProbe>(a, claim, citers, NoProbe{});
+  else
+    csg_sweep<METHOD, NOISE, COLLECT, false, UNROLL, true, NoProbe>(a, claim, citers, NoProbe{});
+}
+
+// The explore sweep (cSGHMC, no noise, no collect) under the drift probe, in
+// the static (DYN = false) or the dynamic order.
+template <int UNROLL, bool DYN>
+__global__ __launch_bounds__(kBlock) void bdl_drift_kernel(const KArgs a, uint32_t* claim,
+                                                           int32_t citers, uint64_t* rec) {
+  DriftProbe p{rec + (size_t)blockIdx.x * BDL_DRIFT_WORDS, 0};
+  if (a.flags & BDL_FLAG_RECIP_DIV)
+    csg_sweep<BDL_CSGHMC, BDL_NOISE_NONE, BDL_COLLECT_NONE, true, UNROLL, DYN, DriftProbe>(
+        a, claim, citers, p);
+  else
+    csg_sweep<BDL_CSGHMC, BDL_NOISE_NONE, BDL_COLLECT_NONE, false, UNROLL, DYN, DriftProbe>(
+        a, claim, citers, p);
+}
+
+// ---------------------------------------------------------------------------
 // Adam-preconditioned SGHMC (methods/adam_sghmc.py:500-553,
 // methods/adam_csghmc.py:812-860) + torch.optim.SGD step + running moments.
 // Same sweep as the SG-MCMC step (run table in LDS, branch-free fast path over
@@ -1564,6 +1741,11 @@ StepKernel pick_noise(int noise, int collect, int unroll) {
 
 StepKernel pick_step_csghmc(int noise, int collect, int unroll);
 StepKernel pick_step_csghmc_bare(int collect, int unroll);
+// the cSGHMC sweeps in the dynamic order (bdl_step_csghmc_dyn.hip) and the drift probe
+using DynKernel = void (*)(const KArgs, uint32_t*, int32_t);
+using DriftKernel = void (*)(const KArgs, uint32_t*, int32_t, uint64_t*);
+DynKernel pick_step_csghmc_dyn(int noise, int collect, int unroll, bool bare);
+DriftKernel pick_drift(int unroll, bool dyn);
 StepKernel pick_step_sghmc(int method, int noise, int collect, int unroll);
 StepKernel pick_step_sgld(int method, int noise, int collect, int unroll);
 StepKernel pick_adam(int noise, int collect, bool grad_only, int unroll);

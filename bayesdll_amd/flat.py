@@ -508,7 +508,8 @@ class FlatState:
         return SimpleNamespace(theta=self.theta[start:end], grad=None, gbase=tab[2], runs=tab[0],
                                nruns=tab[1], mom=sl(self.mom), prior=sl(self.prior), noise=None,
                                n=end - start, device=self.device, nonfinite=self.nonfinite,
-                               extra={k: v[start:end] for k, v in self.extra.items()}, timer=None)
+                               extra={k: v[start:end] for k, v in self.extra.items()}, timer=None,
+                               bucket=True)
 
     def grad_table(self):
         """The run / gradient-base selection of the current step (to reuse

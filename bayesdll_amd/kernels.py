@@ -173,7 +173,7 @@ def _launch(state, fn, a, adam=None, written=None):
             not (a.flags & L.FLAG_FIRST_STEP) and \
             not torch.cuda.is_current_stream_capturing():
         _tune_kind(state, fn, kind, written)
-    _use_geometry(state, kind)
+    _use_geometry(state, kind, sub=getattr(state, "bucket", False))
     t = getattr(state, "timer", None)
     e0 = t.begin() if t is not None else None
     fn()
@@ -276,6 +276,72 @@ def sgmcmc_step_bare(state, **kw):
     a = _step_args(state, L.CSGHMC, **kw)
     L.check(L.lib().bdl_sgmcmc_step_bare(a, L.current_stream_handle(state.device)),
             "bdl_sgmcmc_step_bare")
+
+
+def last_order():
+    """(order, slot) of this thread's last bdl_sgmcmc_step / _bare launch
+    (include/bdl_order.h): 2 only where the launch ran the dynamic order on
+    counter pair `slot`; a launch into a capture or a graph node reports 1."""
+    slot = C.c_int32(-1)
+    return int(L.lib().bdl_order_last(C.byref(slot))), int(slot.value)
+
+
+def order_counters(device=None):
+    """The dynamic order's {claim, done} counters of `device` after a device
+    synchronize, [CLAIM_SLOTS, 2]: all zero between launches."""
+    dev = _device(device)
+    out = (C.c_uint32 * (2 * L.CLAIM_SLOTS))()
+    L.check(L.lib().bdl_order_counters(int(dev.index or 0), out), "bdl_order_counters")
+    return np.ctypeslib.as_array(out).reshape(L.CLAIM_SLOTS, 2).copy()
+
+
+def sweep_drift(state, order, **kw):
+    """One explore sweep of `state` under the drift probe (bdl_sweep_drift,
+    include/bdl_order.h; measurement only, a real cSGHMC step without noise)
+    at the installed workgroups/CU and depth, in sweep order `order`.  Returns
+    the per-workgroup records as an int64 tensor [grid, DRIFT_WORDS] on the
+    host: wall clock (100 MHz) at the first load and after the last store,
+    samples taken, iterations run, then (wall clock, global iteration index)
+    pairs at every DRIFT_EVERY-th iteration.  Synchronous."""
+    a = _step_args(state, L.CSGHMC, noise_mode=L.NOISE_NONE, **kw)
+    cap = 16 * 1024  # more workgroups than any launch geometry has
+    rec = torch.zeros(cap, L.DRIFT_WORDS, dtype=torch.int64, device=state.device)
+    grid = C.c_int32(0)
+    L.check(L.lib().bdl_sweep_drift(a, int(order), rec.data_ptr(),
+                                    rec.numel() * rec.element_size(), C.byref(grid),
+                                    L.current_stream_handle(state.device)), "bdl_sweep_drift")
+    torch.cuda.synchronize(state.device)
+    return rec[:grid.value].cpu()
+
+
+def drift_summary(rec, fractions=(0.125, 0.25, 0.375, 0.5, 0.625, 0.75, 0.875)):
+    """tail_loss = 1 - sum(busy) / (workgroups x span) and, at each fraction of
+    the launch's span, the spread (max - min over workgroups) of the global
+    iteration index each workgroup last sampled, also in sweep rows (/ grid)."""
+    rec = rec.numpy().astype(np.int64)
+    t0, t1, ns = rec[:, 0], rec[:, 1], rec[:, 2]
+    start, end = int(t0.min()), int(t1.max())
+    span = end - start
+    grid = rec.shape[0]
+    out = {"workgroups": int(grid), "span_ticks": int(span),
+           "iterations": int(rec[:, 3].sum()),
+           "iterations_min_max": [int(rec[:, 3].min()), int(rec[:, 3].max())],
+           "tail_loss": float(1.0 - (t1 - t0).sum() / (grid * span)),
+           "ramp_loss": float((t0 - start).sum() / (grid * span)),
+           "end_loss": float((end - t1).sum() / (grid * span)),
+           "truncated": bool((rec[:, 3] > L.DRIFT_EVERY * L.DRIFT_SAMPLES).any()),
+           "spread": []}
+    ts, it = rec[:, 4::2], rec[:, 5::2]
+    valid = np.arange(L.DRIFT_SAMPLES)[None, :] < ns[:, None]
+    for f in fractions:
+        T = start + f * span
+        seen = valid & (ts <= T)
+        have = seen.any(axis=1)
+        last = np.where(seen, it, -1).max(axis=1)[have]
+        sp = int(last.max() - last.min()) if last.size else 0
+        out["spread"].append({"at": f, "iterations": sp, "rows": round(sp / grid, 2),
+                              "workgroups_sampled": int(have.sum())})
+    return out
 
 
 def adam_step(state, method, *, adam_m, adam_v, sgd_buf=None, beta1, beta2, eps, t,
@@ -1891,7 +1957,7 @@ def restore_launch_config(packed):
     return set_launch_config((packed >> 8) & 0xFFFF, packed & 0xFF, (packed >> 24) & 0xFF)
 
 
-def _use_geometry(state, kind="step"):
+def _use_geometry(state, kind="step", sub=False):
     """Install the geometry tuned for this state's size and launch kind
     (state.launch_cfg for plain steps; state.collect_cfg for the steps that
     also read and update the posterior moments, state.init_cfg for a cycle's
@@ -1903,6 +1969,12 @@ def _use_geometry(state, kind="step"):
                   None)
     if cfg is None:
         cfg = getattr(state, "launch_cfg", None)
+    if sub:
+        # the overlap mode's per-bucket launches (FlatState.bucket_state) keep
+        # the grid-stride order: the dynamic order is tuned on whole sweeps
+        act = cfg or _ACTIVE[0]
+        if act is not None and act[2] == L.ORDER_DYNAMIC:
+            cfg = (act[0], act[1], L.ORDER_GRID_STRIDE)
     if cfg is not None and cfg != _ACTIVE[0]:
         set_launch_config(*cfg)
 
@@ -1924,7 +1996,11 @@ AUTOTUNE_BY_METHOD = {
     # 3 x 4 first at ViT-L/32 size (bench.py mix_ceiling, profiles/round4/methods/)
     # + 1 x 1: the bare mix of the explore buffers ran fastest there on the
     # round-5 box (1.038 ms vs 1.064 for the kernel's tuned 1 x 4)
-    "csghmc": AUTOTUNE_CANDIDATES + ((3, 4, 1), (1, 1, 1)),
+    # + every geometry again in the dynamic sweep order (order 2, include/bdl_order.h:
+    # the cSGHMC sweeps only); installed only where it is the fastest on the chain's vectors
+    "csghmc": (AUTOTUNE_CANDIDATES + ((3, 4, 1), (1, 1, 1))
+               + tuple((b, u, L.ORDER_DYNAMIC)
+                       for b, u, _ in AUTOTUNE_CANDIDATES + ((3, 4, 1), (1, 1, 1)))),
     "sgld": AUTOTUNE_CANDIDATES + ((3, 4, 1), (4, 4, 1), (1, 1, 1)),
     "adam": AUTOTUNE_CANDIDATES + ((1, 1, 1), (4, 4, 1)),
 }
@@ -2078,7 +2154,9 @@ def request_state_tuning(state, method):
     ran 2 x 4 fastest on scratch vectors while the bare access mix of the
     chain's own buffers ran 1 x 1 8 % ahead of it, and the Adam sweep's best
     moved from 2 x 4 to 1 x 4 (bench.py mix_ceiling, profiles/round4/methods_b/).
-    BDL_AUTOTUNE=0: the defaults."""
+    cSGHMC: every geometry is tried in the grid-stride and in the dynamic sweep
+    order (AUTOTUNE_BY_METHOD), and the dynamic order is installed, per kind,
+    only where it is the fastest here.  BDL_AUTOTUNE=0: the defaults."""
     if os.environ.get("BDL_AUTOTUNE", "1") == "0" or int(state.n) < TUNE_ON_STATE_MIN:
         return
     state._tune_pending = {"step", "collect", "init"}
@@ -2103,8 +2181,10 @@ def _tune_kind(state, fn, kind, written):
         return
     best, times = tune_on_state(fn, written, cands, state.device)
     setattr(state, {"collect": "collect_cfg", "init": "init_cfg"}.get(kind, "launch_cfg"), best)
-    state.tuned[kind] = {"best": best, "ms": {f"{c[0]}wg/cu x{c[1]}": round(t, 4)
-                                              for c, t in times.items()}}
+    state.tuned[kind] = {"best": best,
+                         "ms": {f"{c[0]}wg/cu x{c[1]}" + (" dynamic" if c[2] == L.ORDER_DYNAMIC
+                                                          else ""): round(t, 4)
+                                for c, t in times.items()}}
 
 
 def tune_on_state(launch, written, candidates, device, reps=4):

@@ -330,7 +330,8 @@ int bdl_philox_normal(float* out, int64_t n, uint64_t seed, uint64_t chain,
 /* Launch geometry override for tuning (0 = default): workgroups per CU, float4
  * groups in flight per lane (1, 2, 4: the production kernels of every method;
  * *_GRAD and noise-free test variants keep 2), and the sweep
- * order (0 = one contiguous span per workgroup, 1 = grid-stride).  Returns the
+ * order (0 = one contiguous span per workgroup, 1 = grid-stride, 2 = claim
+ * blocks taken from a device counter: the cSGHMC sweeps, bdl_order.h).  Returns the
  * previous value packed as (grid_stride << 24) | (blocks_per_cu << 8) | unroll.
  * Process-global, not thread-safe; for tuning and tests. */
 int bdl_set_launch_config(int32_t blocks_per_cu, int32_t unroll, int32_t grid_stride);
