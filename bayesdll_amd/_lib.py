@@ -540,6 +540,43 @@ ORDER_EXPORTS = {
                                   C.POINTER(C.c_int32), C.c_void_p]),
 }
 
+STACK_MAX_VOTERS, STACK_MAX_CLASSES, STACK_MAX_COLS = 64, 8192, 1 << 24
+STACK_TILE, STACK_MAX_GRID, STACK_MAX_CHUNK = 1024, 1024, 65536
+STACK_RESET, STACK_FIRST, STACK_FINAL = 0x1, 0x2, 0x4
+STACK_COUNTERS = ("n_label", "n_nonfinite", "n_impossible")
+
+
+class StackState(C.Structure):
+    """include/bdl_stacking.h bdl_stack_state (one per fit, device memory)."""
+    _fields_ = [("w", C.c_double * STACK_MAX_VOTERS), ("objective", C.c_double),
+                ("gap", C.c_double), ("objective_uniform", C.c_double), ("n", C.c_int64),
+                ("iterations", C.c_int32), ("converged", C.c_int32), ("degenerate", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+class StackGatherArgs(C.Structure):
+    """include/bdl_stacking.h bdl_stack_gather_args."""
+    _fields_ = [("logp", _fp), ("labels", _fp), ("ell", _fp), ("valid", _fp), ("counters", _fp),
+                ("workspace", _fp), ("batch", C.c_int64), ("off", C.c_int64), ("cap", C.c_int64),
+                ("voters", C.c_int32), ("classes", C.c_int32), ("grid_blocks", C.c_int32),
+                ("flags", C.c_int32)]
+
+
+class StackFitArgs(C.Structure):
+    """include/bdl_stacking.h bdl_stack_fit_args."""
+    _fields_ = [("ell", _fp), ("valid", _fp), ("state", _fp), ("workspace", _fp),
+                ("n_cols", C.c_int64), ("cap", C.c_int64), ("tol", C.c_double),
+                ("voters", C.c_int32), ("iterations", C.c_int32), ("grid_blocks", C.c_int32),
+                ("flags", C.c_int32)]
+
+
+# include/bdl_stacking.h: additive to the ABI, as DIAG_EXPORTS
+STACK_EXPORTS = {
+    "bdl_stack_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
+    "bdl_stack_gather": (C.c_int, [C.POINTER(StackGatherArgs), C.c_void_p]),
+    "bdl_stack_fit": (C.c_int, [C.POINTER(StackFitArgs), C.c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -570,7 +607,8 @@ def lib():
                                       + list(MIXTURE_EXPORTS.items())
                                       + list(RANK_EXPORTS.items())
                                       + list(DIVERSITY_EXPORTS.items())
-                                      + list(ORDER_EXPORTS.items())):
+                                      + list(ORDER_EXPORTS.items())
+                                      + list(STACK_EXPORTS.items())):
                 fn = getattr(h, name)
                 fn.restype = res
                 fn.argtypes = argt

@@ -1321,6 +1321,151 @@ def diversity(logits, labels=None, *, totals=None, reset=False, grid_blocks=0):
     return totals
 
 
+def stack_workspace(voters, cols, device):
+    """The cached device scratch of stack_gather / stack_fit for `voters`
+    voters and `cols` columns (bdl_stack_workspace_bytes)."""
+    nbytes = int(L.lib().bdl_stack_workspace_bytes(int(voters), int(cols)))
+    if nbytes <= 0:
+        raise ValueError(f"stacking: 1 <= voters <= {L.STACK_MAX_VOTERS} and 1 <= columns <= "
+                         f"{L.STACK_MAX_COLS} (got {voters}, {cols})")
+    return _scratch(("stacking", device.index, nbytes),
+                    lambda: torch.empty(nbytes, dtype=torch.uint8, device=device))
+
+
+def _stack_matrix(what, ell, valid):
+    """The checks of the resident score matrix: fp32 [P, cap] and int32 [cap]
+    on one HIP device; returns (P, cap)."""
+    if not torch.is_tensor(ell) or ell.dim() != 2 or ell.dtype != torch.float32:
+        raise ValueError(f"{what}: ell must be a float32 [P, cap] tensor")
+    L.require_hip(ell, "ell")
+    P, cap = (int(v) for v in ell.shape)
+    if not ell.is_contiguous() or not 1 <= P <= L.STACK_MAX_VOTERS \
+            or not 1 <= cap <= L.STACK_MAX_COLS:
+        raise ValueError(f"{what}: ell must be contiguous with 1 <= voters <= "
+                         f"{L.STACK_MAX_VOTERS} and 1 <= cap <= {L.STACK_MAX_COLS} (got "
+                         f"{tuple(ell.shape)})")
+    if (not torch.is_tensor(valid) or valid.dtype != torch.int32 or valid.shape != (cap,)
+            or not valid.is_contiguous() or valid.device != ell.device):
+        raise ValueError(f"{what}: valid must be a contiguous int32 [cap] tensor on ell's device")
+    return P, cap
+
+
+def stack_gather(logp, labels, ell, valid, counters, off, *, reset=False, grid_blocks=0):
+    """One batch of the voters' log-probabilities into the resident score
+    matrix of a stacking fit (bdl_stack_gather, include/bdl_stacking.h):
+    ell[p, off + b] = logp[p, b, labels[b]] and valid[off + b] = 1, or a zero
+    column with valid = 0 for an example whose label is outside [0, C), for
+    which a voter gives a NaN or +inf, or for which every voter gives -inf; the
+    three causes are ADDED to `counters` (int64 [3] on the device:
+    _lib.STACK_COUNTERS; reset=True overwrites them).  logp: fp32, contiguous
+    [P, B, C] (predict's `logp` with groups = P); labels: int64 [B].  Two
+    launches on the current stream, no host read.  Returns off + B."""
+    P, cap = _stack_matrix("stack_gather", ell, valid)
+    dev = ell.device
+    if (not torch.is_tensor(logp) or logp.dim() != 3 or logp.dtype != torch.float32
+            or not logp.is_contiguous() or logp.device != dev or int(logp.shape[0]) != P):
+        raise ValueError(f"stack_gather: logp must be a contiguous float32 [{P}, B, C] tensor on "
+                         "ell's device")
+    B, Cn = int(logp.shape[1]), int(logp.shape[2])
+    if B < 1 or not 1 <= Cn <= L.STACK_MAX_CLASSES:
+        raise ValueError(f"stack_gather: batch >= 1 and 1 <= classes <= {L.STACK_MAX_CLASSES} "
+                         f"(got {tuple(logp.shape)})")
+    if (not torch.is_tensor(labels) or labels.dtype != torch.int64 or labels.shape != (B,)
+            or not labels.is_contiguous() or labels.device != dev):
+        raise ValueError("stack_gather: labels must be a contiguous int64 [B] tensor on the logp's "
+                         "device")
+    if (not torch.is_tensor(counters) or counters.dtype != torch.int64 or counters.shape != (3,)
+            or not counters.is_contiguous() or counters.device != dev):
+        raise ValueError("stack_gather: counters must be a contiguous int64 [3] tensor on ell's "
+                         "device")
+    off, grid = int(off), int(grid_blocks)
+    if off < 0 or off + B > cap:
+        raise ValueError(f"stack_gather: columns {off} .. {off + B - 1} do not fit cap = {cap}")
+    if not 0 <= grid <= L.STACK_MAX_GRID:
+        raise ValueError(f"stack_gather: grid_blocks in [0, {L.STACK_MAX_GRID}]")
+    ws = stack_workspace(P, cap, dev)
+    a = L.StackGatherArgs()
+    a.logp, a.labels, a.ell, a.valid = (logp.data_ptr(), labels.data_ptr(), ell.data_ptr(),
+                                        valid.data_ptr())
+    a.counters, a.workspace = counters.data_ptr(), ws.data_ptr()
+    a.batch, a.off, a.cap, a.voters, a.classes, a.grid_blocks = B, off, cap, P, Cn, grid
+    a.flags = L.STACK_RESET if reset else 0
+    L.check(L.lib().bdl_stack_gather(a, L.current_stream_handle(dev)), "bdl_stack_gather")
+    return off + B
+
+
+class StackState:
+    """bdl_stack_state of one stacking fit in device memory.  `read()` /
+    `summary()` is the one host read (w as a float64 [P] array, objective, gap,
+    objective_uniform, n, iterations, converged, degenerate); `weights()` the
+    device fp64 [P] view of w (no host read)."""
+
+    def __init__(self, voters, device):
+        self.voters = int(voters)
+        self.buf = torch.empty(C.sizeof(L.StackState), dtype=torch.uint8, device=device)
+
+    def read(self):
+        return np.frombuffer(self.buf.cpu().numpy().tobytes(), dtype=np.dtype(L.StackState))[0]
+
+    def weights(self):
+        return self.buf.view(torch.float64)[:self.voters]
+
+    def converged_flag(self):
+        """The 4-byte `converged` field (a host read of those 4 bytes only)."""
+        o = L.StackState.converged.offset
+        return int(self.buf[o:o + 4].view(torch.int32).item())
+
+    def summary(self):
+        r = self.read()
+        return {"weights": np.array(r["w"][:self.voters], dtype=np.float64),
+                "objective": float(r["objective"]), "gap": float(r["gap"]),
+                "objective_uniform": float(r["objective_uniform"]), "n": int(r["n"]),
+                "iterations": int(r["iterations"]), "converged": bool(r["converged"]),
+                "degenerate": bool(r["degenerate"])}
+
+
+def stack_fit(ell, valid, n_cols, *, tol=1e-4, max_iter=2000, check_every=128, grid_blocks=0):
+    """Bayesian stacking weights of P voters from their held-out scores, fitted
+    on the device (bdl_stack_fit, include/bdl_stacking.h: the iteration, its
+    arithmetic contract and why `gap` certifies objective* - objective <= gap).
+    ell: fp32 [P, cap] with ell[p, i] = log p_p(y_i | x_i) and valid: int32 [cap]
+    (what stack_gather fills); the first n_cols columns are used.  Up to
+    max_iter (sweep, update) pairs are enqueued back to back on the current
+    stream in chunks of check_every; between chunks the host reads the state's
+    4-byte converged flag and nothing else.  Returns the StackState handle;
+    `.summary()` is the single read of the state."""
+    P, cap = _stack_matrix("stack_fit", ell, valid)
+    N, iters, every, grid, tl = int(n_cols), int(max_iter), int(check_every), int(grid_blocks), \
+        float(tol)
+    if not 1 <= N <= cap:
+        raise ValueError(f"stack_fit: 1 <= n_cols <= cap = {cap} (got {N})")
+    if not tl >= 0.0:
+        raise ValueError(f"stack_fit: tol >= 0 (got {tol})")
+    if iters < 1 or not 1 <= every <= L.STACK_MAX_CHUNK:
+        raise ValueError(f"stack_fit: max_iter >= 1 and 1 <= check_every <= {L.STACK_MAX_CHUNK} "
+                         f"(got {max_iter}, {check_every})")
+    if not 0 <= grid <= L.STACK_MAX_GRID:
+        raise ValueError(f"stack_fit: grid_blocks in [0, {L.STACK_MAX_GRID}]")
+    dev = ell.device
+    ws = stack_workspace(P, N, dev)
+    state = StackState(P, dev)
+    a = L.StackFitArgs()
+    a.ell, a.valid, a.state, a.workspace = (ell.data_ptr(), valid.data_ptr(), state.buf.data_ptr(),
+                                            ws.data_ptr())
+    a.n_cols, a.cap, a.tol, a.voters, a.grid_blocks = N, cap, tl, P, grid
+    h, st = L.lib(), L.current_stream_handle(dev)
+    done = 0
+    while done < iters:
+        a.iterations = min(every, iters - done)
+        done += a.iterations
+        a.flags = (L.STACK_FIRST if done == a.iterations else 0) | \
+            (L.STACK_FINAL if done == iters else 0)
+        L.check(h.bdl_stack_fit(a, st), "bdl_stack_fit")
+        if done < iters and state.converged_flag():
+            break
+    return state
+
+
 def _temper_rows(what, logp, labels, groups, grid_blocks):
     """The checks `temper_fit` and `temper_report` share, worded as predict's;
     returns (G, N, C, grid, workspace)."""

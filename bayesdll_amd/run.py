@@ -161,6 +161,13 @@ def build_parser():
                          "total variation, symmetric KL and double fault, from one fused sweep "
                          "per batch (stacked diversity()); the K x K matrices go to the epoch "
                          "record; works with --sweep")
+    ap.add_argument("--stacking", action="store_true",
+                    help="with --stacked_chains >= 2 and --val_heldout > 0: at every evaluation, "
+                         "fit Bayesian stacking weights of the chains' predictive distributions "
+                         "on the validation split (stacked fit_stacking(): the simplex weights "
+                         "that maximise the held-out log score, fitted on the device), log them "
+                         "with their optimality gap, and score the test split under them "
+                         "(evaluate(..., weights=\"stacking\")); what pools a --sweep")
     ap.add_argument("--gmm_weights", action="store_true",
                     help="with --stacked_chains >= 1 and a cyclical method: at every cycle end, "
                          "score max(1, nst) posterior draws of all chains on the training set "
@@ -275,6 +282,18 @@ def check_gmm_weights(ap, args):
         ap.error(f"--gmm_weights weighs the cycles of a cyclical method (csghmc, csgld, "
                  f"adam_csghmc), not {args.method}")
     return args.gmm_weights
+
+
+def check_stacking(ap, args):
+    """--stacking needs at least two stacked chains and a validation split
+    (ap.error otherwise)."""
+    if args.stacking and args.stacked_chains < 2:
+        ap.error("--stacking weighs the stacked chains against each other: it needs "
+                 "--stacked_chains >= 2")
+    if args.stacking and not args.val_heldout > 0:
+        ap.error("--stacking fits the weights on the validation split: it needs "
+                 "--val_heldout > 0")
+    return args.stacking
 
 
 def check_temperature_scale(ap, args):
@@ -440,6 +459,7 @@ def main(argv=None):
     check_detect(ap, args)
     check_diversity(ap, args)
     check_gmm_weights(ap, args)
+    check_stacking(ap, args)
     check_temperature_scale(ap, args)
     check_by_tensor(ap, args)
     check_fn(ap, args)
@@ -474,6 +494,9 @@ def main(argv=None):
     train_loader, val_loader, test_loader, args.ND = prepare(args, device)
     if args.temperature_scale and val_loader is None:  # before any training is spent
         raise ValueError("--temperature_scale: the validation split is empty "
+                         "(--val_heldout x the training set rounds to 0)")
+    if args.stacking and val_loader is None:  # before any training is spent
+        raise ValueError("--stacking: the validation split is empty "
                          "(--val_heldout x the training set rounds to 0)")
     from .backbones import create_backbone
     net = create_backbone(args)
@@ -520,6 +543,8 @@ def main(argv=None):
                 net0=net0, **kw)
         if args.detect_shift is not None:
             S.detect_shifted = ShiftedLoader(test_loader, args.detect_shift, args.seed)
+        if args.stacking:
+            S.stacking_val = val_loader
         logger.info(f"{args.stacked_chains} stacked chains on this device "
                     f"(chain ids {S.chain0}..{S.chain0 + S.K - 1})")
         hist = S.train(train_loader, test_loader)

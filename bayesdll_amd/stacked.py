@@ -1319,6 +1319,8 @@ class _StackedSampler:
         table kernels.mixture takes: float64 [components, K] by chain,
         [components * K, 1] pooled."""
         from . import chains
+        if weights == "stacking":
+            return self._stacking_weights(what, combine, by_chain)
         if weights != "gmm":
             raise ValueError(f'{what}: weights is None (uniform) or "gmm" (got {weights!r})')
         if combine not in L.MIX_COMBINE:
@@ -1340,12 +1342,135 @@ class _StackedSampler:
             w = w.reshape(-1, 1)
         return torch.from_numpy(np.ascontiguousarray(w)).to(self.args.device)
 
+    # ------------------------------------------------- stacking weights
+    stacking_ = None     # fit_stacking's [K] fp64 device tensor (not checkpointed)
+    stacking_val = None  # run.py --stacking: the validation loader `_report_stacking` fits on
+
+    def fit_stacking(self, loader, *, tol=1e-4, max_iter=2000):
+        """Bayesian stacking of the K chains' predictive distributions (Yao et
+        al. 2018) on a held-out loader, on the device: the weights w on the
+        simplex that maximise the mean log score of sum_k w_k p_k(y | x) — what
+        a per_chain sweep (K different models) or chains in modes of different
+        quality should be pooled with.  A voter is a chain's OWN predictive
+        (`evaluate`'s members, the same Philox keys and the same advance of
+        `draws`): per batch kernels.predict with groups = K, then
+        kernels.stack_gather keeps only every chain's log-probability of the
+        true label, a [K, N] matrix; kernels.stack_fit runs the EM iteration
+        there (include/bdl_stacking.h).  Stores `stacking_` (device fp64 [K];
+        not part of state_dict) for evaluate / uncertainty / fit_temperature
+        (..., weights="stacking") and returns weights (float64 [K]), objective
+        (the mean log score at the weights), objective_uniform (at 1/K),
+        objective_best_single and best_single (the best chain alone), gap
+        (objective* - objective <= gap), iterations, converged, n and the
+        exclusion counts n_label, n_nonfinite, n_impossible.  This process's
+        chains only."""
+        _single_process("fit_stacking")
+        dev, Kc = self.args.device, self.K
+        cap, off, bufs = 4096, 0, {}
+        ell = torch.zeros(Kc, cap, dtype=torch.float32, device=dev)
+        valid = torch.zeros(cap, dtype=torch.int32, device=dev)
+        counters = torch.zeros(3, dtype=torch.int64, device=dev)
+        was = self.net.training
+        self.net.eval()
+        try:
+            for x, y in loader:
+                x, y = x.to(dev), y.to(dev).to(torch.int64).contiguous()
+                outs, _ = K.predict(self._member_logits(x, bufs), y, groups=Kc, want=("logp",))
+                if off + len(y) > cap:  # grow the resident matrix
+                    while off + len(y) > cap:
+                        cap *= 2
+                    ell2 = torch.zeros(Kc, cap, dtype=torch.float32, device=dev)
+                    valid2 = torch.zeros(cap, dtype=torch.int32, device=dev)
+                    ell2[:, :off].copy_(ell[:, :off])
+                    valid2[:off].copy_(valid[:off])
+                    ell, valid = ell2, valid2
+                off = K.stack_gather(outs["logp"], y, ell, valid, counters, off)
+        finally:
+            self.net.train(was)
+        if off == 0:
+            raise ValueError("fit_stacking: the loader is empty")
+        state = K.stack_fit(ell, valid, off, tol=tol, max_iter=max_iter)
+        # every chain's own mean log score, read with the state and the counters
+        ok = valid[:off].bool()
+        single = torch.where(ok, ell[:, :off].double(), torch.zeros((), dtype=torch.float64,
+                                                                    device=dev)).sum(1)
+        both = torch.cat([state.buf, counters.view(torch.uint8),
+                          single.view(torch.uint8)]).cpu().numpy().tobytes()  # the one host read
+        n1 = state.buf.numel()
+        r = np.frombuffer(both[:n1], dtype=np.dtype(L.StackState))[0]
+        cnt = np.frombuffer(both[n1:n1 + 24], dtype=np.int64)
+        n = int(r["n"])
+        if n == 0:
+            raise ValueError("fit_stacking: no example can be scored (n = 0: "
+                             + ", ".join(f"{k} = {int(v)}" for k, v in zip(L.STACK_COUNTERS, cnt))
+                             + ")")
+        if r["degenerate"]:
+            raise ValueError("fit_stacking: the fit is degenerate (a mixture probability "
+                             "underflowed)")
+        single = np.frombuffer(both[n1 + 24:], dtype=np.float64) / n
+        best = int(np.argmax(np.where(np.isfinite(single), single, -np.inf)))
+        self.stacking_ = state.weights().clone()
+        res = {"weights": np.array(r["w"][:Kc], dtype=np.float64),
+               "objective": float(r["objective"]),
+               "objective_uniform": float(r["objective_uniform"]),
+               "objective_best_single": float(single[best]), "best_single": self.chain0 + best,
+               "iterations": int(r["iterations"]), "converged": bool(r["converged"]),
+               "gap": float(r["gap"]), "n": n}
+        res.update({k: int(v) for k, v in zip(L.STACK_COUNTERS, cnt)})
+        return res
+
+    def _stacking_weights(self, what, combine, by_chain):
+        """The refusals of weights="stacking", then kernels.mixture's pooled
+        table: float64 [components * K, 1] with w_{c,k} = w_k / components, so
+        that the arithmetic mixture is exactly sum_k w_k p_k."""
+        from . import chains
+        if combine not in L.MIX_COMBINE:
+            raise ValueError(f"{what}: combine from {tuple(L.MIX_COMBINE)} (got {combine!r})")
+        if chains.world() > 1:
+            raise ValueError(f'{what}: weights="stacking" weighs this process\'s chains only, and '
+                             f"{chains.world()} processes share the predictive")
+        if by_chain:
+            raise ValueError(f'{what}: weights="stacking" weighs the chains against each other: '
+                             "it is the pooled form only (there is nothing to weigh within one "
+                             "chain)")
+        if combine == "reference":
+            raise ValueError(f'{what}: combine="reference" is one Runner\'s rule (a weighted sum '
+                             "of ITS cycles' log-probabilities); stacking weights maximise the "
+                             "log score of the arithmetic mixture")
+        if self.stacking_ is None:
+            raise ValueError(f'{what}: weights="stacking" needs a fit_stacking() first')
+        comps = max(1, len(self._component_keys()))
+        w = (self.stacking_ / comps).repeat(comps)  # [components, K] row-major
+        return w.reshape(-1, 1).contiguous()
+
+    def _report_stacking(self, ep, rec, val_loader, test_loader, log):
+        """run.py --stacking: fit on the validation split, log the weights
+        line, and with a test loader the stacked predictive under them
+        (rec["stacking"], rec["test_stacking"])."""
+        try:
+            d = self.fit_stacking(val_loader)
+            rec["stacking"] = {k: (v.tolist() if isinstance(v, np.ndarray) else v)
+                               for k, v in d.items()}
+            log(f"(Epoch {ep}) stacking weights: "
+                f"{ {self.chain0 + k: float(w) for k, w in enumerate(d['weights'])} } "
+                f"(gap = {d['gap']:.2e}, iterations = {d['iterations']}, converged = "
+                f"{d['converged']})")
+            if test_loader is None:
+                return
+            rec["test_stacking"] = self.evaluate(test_loader, weights="stacking")
+            log(f"(Epoch {ep}) stacked predictive, stacking weights: loss = "
+                f"{rec['test_stacking'][0]:.4f}, error = {rec['test_stacking'][1]:.4f}")
+        except ValueError as e:
+            log(f"(Epoch {ep}) stacking weights: {e}")
+
     def _weighted_batches(self, what, loader, weights, combine, by_chain, want=("logp",)):
         """Per batch of the loader (eval mode): (mixture outputs, labels,
         MixtureTotals) of the weighted predictive — `evaluate`'s members, the
         same Philox keys and the same advance of `draws`."""
         wdev = self._mixture_weights(what, weights, combine, by_chain)
         dev, nd, bufs, tot = self.args.device, max(1, self.nst), {}, None
+        if not self._component_keys():  # nothing collected: the chains' current theta, one draw
+            nd = 1
         was = self.net.training
         self.net.eval()
         try:
@@ -1591,6 +1716,8 @@ class _StackedSampler:
         res = {k: [r[k] for r in rows] for k in rows[0]} if by_chain else rows[0]
         comps = len(self._component_keys())
         res["members"] = comps * max(1, self.nst) * (1 if by_chain else self.K)
+        if not comps:  # weights="stacking" with nothing collected: the K current thetas
+            res["members"] = self.K
         res["num_bins"], res["combine"] = nb, combine
         return res
 
@@ -1892,6 +2019,9 @@ class _StackedSampler:
                     self._report_detection(ep, rec, test_loader, log)
                 if getattr(self.args, "diversity", False):  # opt-in (run.py --diversity)
                     self._report_diversity(ep, rec, test_loader, log)
+                if getattr(self.args, "stacking", False) and self.stacking_val is not None:
+                    # opt-in (run.py --stacking)
+                    self._report_stacking(ep, rec, self.stacking_val, test_loader, log)
                 if self.per_chain is not None:
                     self._report_chains(ep, rec, test_loader, log)
                 if getattr(self.args, "rhat", False):  # opt-in (run.py --rhat)
