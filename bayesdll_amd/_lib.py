@@ -577,6 +577,52 @@ STACK_EXPORTS = {
     "bdl_stack_fit": (C.c_int, [C.POINTER(StackFitArgs), C.c_void_p]),
 }
 
+EXCHANGE_MAX_CHAINS, EXCHANGE_MAX_VECTORS, EXCHANGE_TILE, EXCHANGE_MAX_GRID = 64, 4, 1024, 65535
+EXCHANGE_STEP_BASE = 1 << 63  # Philox step domain of the exchange draws (include/bdl_exchange.h)
+EXCHANGE_FIRST, EXCHANGE_ENERGY_ONLY = 0x1, 0x2
+EXCHANGE_UP, EXCHANGE_DOWN = 1, 2
+
+
+class ExchangeState(C.Structure):
+    """include/bdl_exchange.h bdl_exchange_state (device memory)."""
+    _fields_ = [("q", C.c_double * EXCHANGE_MAX_CHAINS), ("U", C.c_double * EXCHANGE_MAX_CHAINS),
+                ("attempts", C.c_uint64 * EXCHANGE_MAX_CHAINS),
+                ("accepts", C.c_uint64 * EXCHANGE_MAX_CHAINS),
+                ("round_trips", C.c_uint64 * EXCHANGE_MAX_CHAINS), ("refused", C.c_uint64),
+                ("partner", C.c_int32 * EXCHANGE_MAX_CHAINS),
+                ("replica", C.c_int32 * EXCHANGE_MAX_CHAINS),
+                ("direction", C.c_int32 * EXCHANGE_MAX_CHAINS)]
+
+
+class ExchangeEnergyArgs(C.Structure):
+    """include/bdl_exchange.h bdl_exchange_energy_args."""
+    _fields_ = [("theta", _fp), ("prior", _fp), ("workspace", _fp), ("n", C.c_int64),
+                ("chain_groups", C.c_uint64), ("chains", C.c_int32), ("grid_blocks", C.c_int32)]
+
+
+class ExchangeDecideArgs(C.Structure):
+    """include/bdl_exchange.h bdl_exchange_decide_args."""
+    _fields_ = [("state", _fp), ("workspace", _fp), ("loss", _fp), ("beta", _fp),
+                ("n", C.c_int64), ("n_data", C.c_double), ("sigma2", C.c_double),
+                ("var", C.c_double), ("seed", C.c_uint64), ("chain0", C.c_uint64),
+                ("attempt", C.c_uint64), ("chains", C.c_int32), ("flags", C.c_int32)]
+
+
+class ExchangeSwapArgs(C.Structure):
+    """include/bdl_exchange.h bdl_exchange_swap_args."""
+    _fields_ = [("state", _fp), ("vectors", _fp * EXCHANGE_MAX_VECTORS),
+                ("chain_groups", C.c_uint64), ("nvectors", C.c_int32), ("chains", C.c_int32),
+                ("grid_blocks", C.c_int32), ("pad", C.c_int32)]
+
+
+# include/bdl_exchange.h: additive to the ABI, as DIAG_EXPORTS
+EXCHANGE_EXPORTS = {
+    "bdl_exchange_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
+    "bdl_exchange_energy": (C.c_int, [C.POINTER(ExchangeEnergyArgs), C.c_void_p]),
+    "bdl_exchange_decide": (C.c_int, [C.POINTER(ExchangeDecideArgs), C.c_void_p]),
+    "bdl_exchange_swap": (C.c_int, [C.POINTER(ExchangeSwapArgs), C.c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -608,7 +654,8 @@ def lib():
                                       + list(RANK_EXPORTS.items())
                                       + list(DIVERSITY_EXPORTS.items())
                                       + list(ORDER_EXPORTS.items())
-                                      + list(STACK_EXPORTS.items())):
+                                      + list(STACK_EXPORTS.items())
+                                      + list(EXCHANGE_EXPORTS.items())):
                 fn = getattr(h, name)
                 fn.restype = res
                 fn.argtypes = argt

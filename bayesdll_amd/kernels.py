@@ -1466,6 +1466,146 @@ def stack_fit(ell, valid, n_cols, *, tol=1e-4, max_iter=2000, check_every=128, g
     return state
 
 
+def _exchange_chains_error(chains):
+    if not 1 <= chains <= L.EXCHANGE_MAX_CHAINS:
+        return f"1 <= chains <= {L.EXCHANGE_MAX_CHAINS} is required"
+    return None
+
+
+def exchange_workspace(chains, n, device):
+    """The cached device partials of exchange_energy / exchange_decide for
+    `chains` chains of `n` elements (bdl_exchange_workspace_bytes)."""
+    nbytes = int(L.lib().bdl_exchange_workspace_bytes(int(chains), int(n)))
+    if nbytes <= 0:
+        raise ValueError(f"exchange: 1 <= chains <= {L.EXCHANGE_MAX_CHAINS} and n >= 1 (got "
+                         f"{chains}, {n})")
+    return _scratch(("exchange", device.index, nbytes),
+                    lambda: torch.empty(nbytes, dtype=torch.uint8, device=device))
+
+
+class ExchangeState:
+    """bdl_exchange_state of one ladder of `chains` stacked chains in device
+    memory (include/bdl_exchange.h).  `fresh`: the next exchange_decide
+    initialises it (BDL_EXCHANGE_FIRST).  `read()` / `summary()` is the one
+    host read; `q()` the device fp64 [chains] view of the last energies' prior
+    part (no host read)."""
+
+    def __init__(self, chains, device):
+        self.chains = int(chains)
+        why = _exchange_chains_error(self.chains)
+        if why:
+            raise ValueError(f"ExchangeState: {why}")
+        self.buf = torch.zeros(C.sizeof(L.ExchangeState), dtype=torch.uint8, device=device)
+        self.fresh = True
+
+    def read(self):
+        return np.frombuffer(self.buf.cpu().numpy().tobytes(), dtype=np.dtype(L.ExchangeState))[0]
+
+    def q(self):
+        return self.buf.view(torch.float64)[:self.chains]
+
+    def summary(self):
+        r, Kc = self.read(), self.chains
+        return {"q": np.array(r["q"][:Kc]), "U": np.array(r["U"][:Kc]),
+                "attempts": np.array(r["attempts"][:max(Kc - 1, 0)]),
+                "accepts": np.array(r["accepts"][:max(Kc - 1, 0)]),
+                "round_trips": np.array(r["round_trips"][:Kc]), "refused": int(r["refused"]),
+                "partner": np.array(r["partner"][:Kc]), "replica": np.array(r["replica"][:Kc]),
+                "direction": np.array(r["direction"][:Kc])}
+
+
+def exchange_energy(theta, prior, *, chains, chain_groups, n, grid_blocks=0):
+    """The (chain, tile) partials of q_k = sum_i (theta_k[i] - prior_k[i])^2
+    over each chain's n real elements (bdl_exchange_energy,
+    include/bdl_exchange.h: fp32 difference, fp64 square and sums over fixed
+    tiles of 1024 elements in a literal order; prior None: theta0 = 0).  One
+    launch on the current stream; `exchange_decide` adds the partials.  Returns
+    the workspace."""
+    vecs = [("theta", theta)] + ([] if prior is None else [("prior", prior)])
+    chains, chain_groups, n, dev = _stacked_layout("exchange_energy", vecs, chains, chain_groups, n,
+                                                   chains_error=_exchange_chains_error)
+    for nm, t in vecs:
+        if t.dtype != torch.float32:
+            raise ValueError(f"exchange_energy: {nm} must be float32")
+    grid = int(grid_blocks)
+    if not 0 <= grid <= L.EXCHANGE_MAX_GRID:
+        raise ValueError(f"exchange_energy: grid_blocks in [0, {L.EXCHANGE_MAX_GRID}]")
+    ws = exchange_workspace(chains, n, dev)
+    a = L.ExchangeEnergyArgs()
+    a.theta, a.prior = theta.data_ptr(), None if prior is None else prior.data_ptr()
+    a.workspace, a.n, a.chain_groups, a.chains, a.grid_blocks = (ws.data_ptr(), n, chain_groups,
+                                                                 chains, grid)
+    L.check(L.lib().bdl_exchange_energy(a, L.current_stream_handle(dev)), "bdl_exchange_energy")
+    return ws
+
+
+def exchange_decide(state, workspace, loss=None, beta=None, *, n, n_data=1.0, sigma2=1.0, var=0.0,
+                    seed=0, chain0=0, attempt=0, energy_only=False):
+    """Attempt `attempt` of the deterministic even-odd exchange between
+    adjacent slots (bdl_exchange_decide, include/bdl_exchange.h): q_k from the
+    partials in the fixed order, U_k = n_data * loss[k] + q_k / (2 sigma2), the
+    Metropolis rule with one Philox word per pair in the exchange step domain,
+    partner / replica / counters / round trips in `state`.  loss: device fp32
+    [chains]; beta: device fp64 [chains] (1 / T_k).  energy_only: only state.q
+    is formed (loss and beta are not read).  One launch, no host read."""
+    if not isinstance(state, ExchangeState):
+        raise ValueError("exchange_decide: state must be an ExchangeState")
+    dev, Kc = state.buf.device, state.chains
+    if not torch.is_tensor(workspace) or workspace.device != dev or workspace.numel() < \
+            int(L.lib().bdl_exchange_workspace_bytes(Kc, int(n))) or int(n) < 1:
+        raise ValueError("exchange_decide: workspace must be exchange_energy's for (chains, n)")
+    if not energy_only:
+        for nm, t, dt in (("loss", loss, torch.float32), ("beta", beta, torch.float64)):
+            if (not torch.is_tensor(t) or t.dtype != dt or t.shape != (Kc,) or not t.is_contiguous()
+                    or t.device != dev):
+                raise ValueError(f"exchange_decide: {nm} must be a contiguous {dt} [{Kc}] tensor "
+                                 "on the state's device")
+        if not float(sigma2) > 0 or not float(var) >= 0:
+            raise ValueError(f"exchange_decide: sigma2 > 0 and var >= 0 (got {sigma2}, {var})")
+        if not 0 <= int(attempt) < 1 << 62:
+            raise ValueError("exchange_decide: 0 <= attempt < 2^62")
+    a = L.ExchangeDecideArgs()
+    a.state, a.workspace = state.buf.data_ptr(), workspace.data_ptr()
+    a.loss = None if energy_only else loss.data_ptr()
+    a.beta = None if energy_only else beta.data_ptr()
+    a.n, a.n_data, a.sigma2, a.var = int(n), float(n_data), float(sigma2), float(var)
+    a.seed, a.chain0 = int(seed) & (2 ** 64 - 1), int(chain0) & (2 ** 64 - 1)
+    a.attempt, a.chains = int(attempt), Kc
+    a.flags = L.EXCHANGE_ENERGY_ONLY if energy_only else \
+        (L.EXCHANGE_FIRST if state.fresh else 0)
+    L.check(L.lib().bdl_exchange_decide(a, L.current_stream_handle(dev)), "bdl_exchange_decide")
+    if not energy_only:
+        state.fresh = False
+
+
+def exchange_swap(state, vectors, *, chain_groups, grid_blocks=0):
+    """Exchange the whole chain slots (padding included) of every pair
+    `state.partner` accepted, in each of the 1 .. 4 stacked fp32 `vectors`
+    (bdl_exchange_swap, include/bdl_exchange.h).  One launch, no host read."""
+    if not isinstance(state, ExchangeState):
+        raise ValueError("exchange_swap: state must be an ExchangeState")
+    vectors = list(vectors)
+    if not 1 <= len(vectors) <= L.EXCHANGE_MAX_VECTORS:
+        raise ValueError(f"exchange_swap: 1 .. {L.EXCHANGE_MAX_VECTORS} vectors (got "
+                         f"{len(vectors)})")
+    vecs = [(f"vectors[{i}]", v) for i, v in enumerate(vectors)]
+    chains, chain_groups, _, dev = _stacked_layout("exchange_swap", vecs, state.chains, chain_groups,
+                                                   4 * int(chain_groups),
+                                                   chains_error=_exchange_chains_error)
+    for nm, t in vecs:
+        if t.dtype != torch.float32 or t.device != state.buf.device:
+            raise ValueError(f"exchange_swap: {nm} must be float32 on the state's device")
+    grid = int(grid_blocks)
+    if not 0 <= grid <= L.EXCHANGE_MAX_GRID:
+        raise ValueError(f"exchange_swap: grid_blocks in [0, {L.EXCHANGE_MAX_GRID}]")
+    a = L.ExchangeSwapArgs()
+    a.state = state.buf.data_ptr()
+    for i, v in enumerate(vectors):
+        a.vectors[i] = v.data_ptr()
+    a.chain_groups, a.nvectors, a.chains, a.grid_blocks = chain_groups, len(vectors), chains, grid
+    L.check(L.lib().bdl_exchange_swap(a, L.current_stream_handle(dev)), "bdl_exchange_swap")
+
+
 def _temper_rows(what, logp, labels, groups, grid_blocks):
     """The checks `temper_fit` and `temper_report` share, worded as predict's;
     returns (G, N, C, grid, workspace)."""

@@ -168,6 +168,16 @@ def build_parser():
                          "that maximise the held-out log score, fitted on the device), log them "
                          "with their optimality gap, and score the test split under them "
                          "(evaluate(..., weights=\"stacking\")); what pools a --sweep")
+    ap.add_argument("--exchange", type=int, default=0, metavar="M",
+                    help="with --stacked_chains >= 2, --method sgld or csgld, --momentum 0 and "
+                         "--sweep nd=...: replica exchange (parallel tempering) between the "
+                         "chains, whose temperatures are T_k = nd_k^2 — after every M-th step one "
+                         "extra forward and three launches attempt to swap adjacent slots "
+                         "(even-odd Metropolis, no host read); one log line per evaluation and "
+                         "the record in the epoch record (stacked exchange())")
+    ap.add_argument("--exchange_var", type=float, default=0.0, metavar="V",
+                    help="with --exchange: the variance correction of noisy minibatch energies "
+                         "(log acceptance -= (1/T_i - 1/T_j)^2 * V; 0: the plain Metropolis rule)")
     ap.add_argument("--gmm_weights", action="store_true",
                     help="with --stacked_chains >= 1 and a cyclical method: at every cycle end, "
                          "score max(1, nst) posterior draws of all chains on the training set "
@@ -282,6 +292,32 @@ def check_gmm_weights(ap, args):
         ap.error(f"--gmm_weights weighs the cycles of a cyclical method (csghmc, csgld, "
                  f"adam_csghmc), not {args.method}")
     return args.gmm_weights
+
+
+def check_exchange(ap, args):
+    """--exchange needs stacked SGLD / cSGLD chains with an nd ladder (ap.error
+    otherwise; the sampler checks the ladder itself)."""
+    if args.exchange_var != 0.0 and not args.exchange:
+        ap.error("--exchange_var corrects the exchange rule: it needs --exchange M")
+    if not args.exchange:
+        return 0
+    if args.exchange < 0:
+        ap.error("--exchange M: M must be >= 1 (steps between exchange attempts)")
+    if not args.exchange_var >= 0.0:
+        ap.error("--exchange_var must be >= 0")
+    if args.stacked_chains < 2:
+        ap.error("--exchange swaps the stacked chains of one device: it needs "
+                 "--stacked_chains >= 2")
+    if args.method not in ("sgld", "csgld"):
+        ap.error(f"--exchange: no temperature is derived for {args.method} (sgld or csgld)")
+    if not any(item.split("=", 1)[0].strip() == "nd" for item in args.sweep):
+        ap.error("--exchange needs a temperature ladder: it needs --sweep nd=v1,...,vK "
+                 "(T_k = nd_k^2)")
+    if args.momentum != 0 and not any(item.split("=", 1)[0].strip() == "momentum"
+                                      for item in args.sweep):
+        ap.error("--exchange needs --momentum 0 (with SGD momentum a chain does not sample "
+                 "exp(-U / nd^2))")
+    return args.exchange
 
 
 def check_stacking(ap, args):
@@ -460,6 +496,7 @@ def main(argv=None):
     check_diversity(ap, args)
     check_gmm_weights(ap, args)
     check_stacking(ap, args)
+    check_exchange(ap, args)
     check_temperature_scale(ap, args)
     check_by_tensor(ap, args)
     check_fn(ap, args)
@@ -536,6 +573,8 @@ def main(argv=None):
             kw["health_every"] = args.health
         if args.ess:
             kw["ess_batch"] = args.ess
+        if args.exchange:
+            kw["exchange_every"], kw["exchange_var"] = args.exchange, args.exchange_var
         if args.fn_probe:
             kw["fn_probe"] = first_examples(test_loader, args.fn_probe)
             kw["fn_batch"] = args.fn_batch

@@ -436,12 +436,15 @@ class _StackedSampler:
 
     def __init__(self, net, K_, args, *, chain0=None, seed=None, init="copy", criterion=None,
                  per_chain_batches=False, logger=None, graph=None, net0=None, per_chain=None,
-                 health_every=0, ess_batch=0, fn_probe=None, fn_batch=0):
+                 health_every=0, ess_batch=0, fn_probe=None, fn_batch=0, exchange_every=0,
+                 exchange_var=0.0):
         from . import chains
         from ._base import default_compute_dtype, default_graph, refuse_compute_dtype
         refuse_compute_dtype(getattr(args, "compute_dtype", None) or default_compute_dtype(),
                              "the stacked samplers (bayesdll_amd.stacked)")
+        self._check_exchange_sampler(exchange_every)
         self._init_per_chain(per_chain, K_, args)
+        self._init_exchange(exchange_every, exchange_var, K_, per_chain_batches, net, args)
         self.gmm_weights = bool(getattr(args, "gmm_weights", False))
         if self.gmm_weights and not self.cyclical:
             raise ValueError(f"{type(self).__name__}: gmm_weights weighs the cycles of a cyclical "
@@ -503,6 +506,10 @@ class _StackedSampler:
                 self.state.collect_cfg = K.collect_config(self.state.n, self.state.device,
                                                           self.tune_method)
         self.criterion = criterion or torch.nn.CrossEntropyLoss()
+        if self.exchange_every:
+            self._xstate = K.ExchangeState(K_, self.state.device)
+            self._xbeta = torch.tensor(1.0 / self.per_chain["nd"] ** 2, dtype=torch.float64,
+                                       device=self.state.device)
         self.step_count = 0
         self.draws = 0
         st = self.state
@@ -589,7 +596,151 @@ class _StackedSampler:
             self._ess_fold(kw["collect"][0])
         if self._fn_probe is not None and kw.get("collect") is not None:
             self._fn_fold()
+        if self.exchange_every and self.step_count % self.exchange_every == 0:
+            self._exchange_attempt(x, y)
         return loss, out
+
+    # ------------------------------------------------------ replica exchange
+    exchange_ok = False  # the samplers a temperature is derived for (SGLD / cSGLD)
+    exchange_every = 0   # an exchange attempt after every m-th step (0: never)
+    exchange_var = 0.0
+    _xstate = _xbeta = None
+    _xattempt = 0
+
+    def _check_exchange_sampler(self, every):
+        if int(every) != every or int(every) < 0:
+            raise ValueError(f"exchange_every must be an integer >= 0 (got {every!r})")
+        if every and not self.exchange_ok:
+            raise ValueError(f"{type(self).__name__}: exchange_every needs a temperature per "
+                             "chain, and none is derived for this sampler (cSGHMC, SGHMC and the "
+                             "Adam samplers: only SGLD / cSGLD with momentum 0 sample "
+                             "exp(-U / nd^2))")
+
+    def _init_exchange(self, every, var, K_, per_chain_batches, net, args):
+        """Validate replica exchange before anything touches the device: the K
+        chains must be one target at K temperatures T_k = nd_k^2, and the
+        energy of the exchange rule must be the one the update descends."""
+        import torch.nn as nn
+        from . import chains
+        if not every:
+            return
+        who = f"{type(self).__name__}: exchange_every"
+        bias = str(args.hparams["bias"])
+        if bias != "informative":
+            raise ValueError(f"{who}: bias={bias!r}: the update puts no prior on the bias "
+                             "tensors, but the exchange energy sums (theta - theta0)^2 over every "
+                             "element; only bias='informative' makes them the same target")
+        frozen = [nm for nm, p in net.named_parameters() if not p.requires_grad]
+        if frozen:
+            raise ValueError(f"{who}: frozen tensors ({', '.join(frozen[:3])}"
+                             f"{', ...' if len(frozen) > 3 else ''}): they are not sampled, yet "
+                             "they would enter the energy and travel with a swap")
+        drop = [nm for nm, m in net.named_modules() if isinstance(m, nn.modules.dropout._DropoutNd)]
+        if drop:
+            raise ValueError(f"{who}: dropout layers ({', '.join(drop[:3])}): the extra forward "
+                             "would give a randomly masked energy and consume torch's generator")
+        if not float(var) >= 0.0:
+            raise ValueError(f"{who}: exchange_var must be >= 0 (got {var!r})")
+        if self.per_chain is None:
+            raise ValueError(f"{who} needs a per_chain table with an nd ladder (no per_chain: "
+                             "every chain has the same temperature)")
+        pc = self.per_chain
+        if (pc["momentum"] != 0).any():
+            raise ValueError(f"{who} needs momentum == 0: with SGD momentum chain k does not "
+                             "sample exp(-U / nd_k^2)")
+        for nm in ("prior_sig", "Ninflate"):
+            if (pc[nm] != pc[nm][0]).any():
+                raise ValueError(f"{who}: {nm} differs between chains, so their targets differ "
+                                 "in more than temperature")
+        nd = pc["nd"]
+        if not (nd > 0).all():
+            raise ValueError(f"{who}: every nd must be > 0 (T = nd^2 is a temperature)")
+        d = np.diff(nd)
+        if K_ > 1 and not ((d > 0).all() or (d < 0).all()):
+            raise ValueError(f"{who}: nd must be strictly monotone in slot order (the ladder "
+                             "order is the slot order)")
+        if per_chain_batches:
+            raise ValueError(f"{who}: one batch per chain (per_chain_batches): the energies of a "
+                             "pair must come from the same batch")
+        if chains.world() > 1:
+            raise ValueError(f"{who}: {chains.world()} processes: the ladder is this process's "
+                             "chains only")
+        if K_ > L.EXCHANGE_MAX_CHAINS:
+            raise ValueError(f"{who}: at most {L.EXCHANGE_MAX_CHAINS} chains")
+        self.exchange_every, self.exchange_var = int(every), float(var)
+
+    def _exchange_attempt(self, x, y):
+        """One exchange attempt after `update`: an extra no_grad vmapped
+        forward on the same batch gives every chain's mean loss at the updated
+        theta (eager also in graph mode), then the three launches of
+        include/bdl_exchange.h back to back.  No host read."""
+        st = self.state
+        crit = self.criterion
+        with torch.no_grad():
+            out = self._fwd(st.params, x)
+            loss = torch.stack([crit(out[k], y) for k in range(self.K)]).float().contiguous()
+        N = self.args.ND * float(self.per_chain["Ninflate"][0])
+        ws = K.exchange_energy(st.theta, st.prior, chains=self.K, chain_groups=st.chain_groups,
+                               n=st.n1)
+        K.exchange_decide(self._xstate, ws, loss, self._xbeta, n=st.n1, n_data=N,
+                          sigma2=float(self.per_chain["prior_sig"][0]) ** 2,
+                          var=self.exchange_var, seed=self.seed, chain0=self.chain0,
+                          attempt=self._xattempt)
+        # momentum == 0 is required, so the launch neither reads nor writes the SGD
+        # buffer: theta is the whole of a replica's state
+        K.exchange_swap(self._xstate, [st.theta], chain_groups=st.chain_groups)
+        self._xattempt += 1
+
+    def cold_slots(self):
+        """The slots whose nd is the minimum (the target's own temperature)."""
+        if self.per_chain is None:
+            raise ValueError("cold_slots: no per_chain table (every chain has the same nd)")
+        nd = self.per_chain["nd"]
+        return [int(k) for k in np.flatnonzero(nd == nd.min())]
+
+    def exchange(self):
+        """The replica-exchange record (one host read): per adjacent pair the
+        attempts, accepts, rate and both temperatures; `replica` (which initial
+        replica sits in which slot), `round_trips` per replica and in total,
+        `refused` (attempts with a non-finite energy), `attempt` and `cold`."""
+        if not self.exchange_every:
+            raise ValueError("exchange: exchange_every is 0 (replica exchange is off)")
+        d = self._xstate.summary()
+        T = self.per_chain["nd"] ** 2
+        if self._xstate.fresh:  # no attempt yet: the state is still zeros
+            d["replica"] = np.arange(self.K)
+        pairs = [{"slots": (i, i + 1), "attempts": int(d["attempts"][i]),
+                  "accepts": int(d["accepts"][i]),
+                  "rate": float(d["accepts"][i]) / max(1, int(d["attempts"][i])),
+                  "temperatures": (float(T[i]), float(T[i + 1]))} for i in range(self.K - 1)]
+        return {"pairs": pairs, "replica": [int(r) for r in d["replica"]],
+                "round_trips": [int(r) for r in d["round_trips"]],
+                "round_trips_total": int(d["round_trips"].sum()), "refused": d["refused"],
+                "attempt": self._xattempt, "cold": self.cold_slots()}
+
+    def _exchange_ckpt(self):
+        """The exchange state for `_extra_state`, only when the option is on."""
+        if not self.exchange_every:
+            return {}
+        return {"exchange_state": self._xstate.buf.clone(), "exchange_attempt": self._xattempt,
+                "exchange_fresh": self._xstate.fresh}
+
+    def _load_exchange_ckpt(self, d):
+        if not self.exchange_every:
+            return
+        if "exchange_state" not in d:
+            raise ValueError("load_ckpt: the checkpoint was written without exchange_every")
+        self._xstate.buf.copy_(d["exchange_state"])
+        self._xattempt, self._xstate.fresh = int(d["exchange_attempt"]), bool(d["exchange_fresh"])
+
+    def _report_exchange(self, ep, rec, log):
+        """run.py --exchange: one log line per evaluation and rec["exchange"]."""
+        d = rec["exchange"] = self.exchange()
+        rates = ", ".join(f"{p['slots'][0]}-{p['slots'][1]}: {p['accepts']}/{p['attempts']}"
+                          for p in d["pairs"])
+        log(f"(Epoch {ep}) replica exchange after {d['attempt']} attempts: accepted {rates}; "
+            f"replica = {d['replica']}, round trips = {d['round_trips_total']}, refused = "
+            f"{d['refused']}")
 
     # ------------------------------------------------------------------ ess
     def _ess_fold(self, kind):
@@ -1321,6 +1472,8 @@ class _StackedSampler:
         from . import chains
         if weights == "stacking":
             return self._stacking_weights(what, combine, by_chain)
+        if weights == "cold":
+            return self._stacking_weights(what, combine, by_chain, cold=True)
         if weights != "gmm":
             raise ValueError(f'{what}: weights is None (uniform) or "gmm" (got {weights!r})')
         if combine not in L.MIX_COMBINE:
@@ -1419,28 +1572,43 @@ class _StackedSampler:
         res.update({k: int(v) for k, v in zip(L.STACK_COUNTERS, cnt)})
         return res
 
-    def _stacking_weights(self, what, combine, by_chain):
+    def _stacking_weights(self, what, combine, by_chain, cold=False):
         """The refusals of weights="stacking", then kernels.mixture's pooled
         table: float64 [components * K, 1] with w_{c,k} = w_k / components, so
-        that the arithmetic mixture is exactly sum_k w_k p_k."""
+        that the arithmetic mixture is exactly sum_k w_k p_k.  cold
+        (weights="cold"): the same refusals and the same table with w = 1 on
+        the cold slot (`cold_slots`; shared equally if several) and 0 elsewhere."""
         from . import chains
+        kind = "cold" if cold else "stacking"
         if combine not in L.MIX_COMBINE:
             raise ValueError(f"{what}: combine from {tuple(L.MIX_COMBINE)} (got {combine!r})")
         if chains.world() > 1:
-            raise ValueError(f'{what}: weights="stacking" weighs this process\'s chains only, and '
+            raise ValueError(f'{what}: weights="{kind}" weighs this process\'s chains only, and '
                              f"{chains.world()} processes share the predictive")
         if by_chain:
-            raise ValueError(f'{what}: weights="stacking" weighs the chains against each other: '
+            raise ValueError(f'{what}: weights="{kind}" weighs the chains against each other: '
                              "it is the pooled form only (there is nothing to weigh within one "
                              "chain)")
         if combine == "reference":
             raise ValueError(f'{what}: combine="reference" is one Runner\'s rule (a weighted sum '
-                             "of ITS cycles' log-probabilities); stacking weights maximise the "
-                             "log score of the arithmetic mixture")
-        if self.stacking_ is None:
-            raise ValueError(f'{what}: weights="stacking" needs a fit_stacking() first')
+                             "of ITS cycles' log-probabilities); "
+                             + ("the cold slot's weight is a weight of the arithmetic mixture"
+                                if cold else "stacking weights maximise the log score of the "
+                                "arithmetic mixture"))
+        if cold:
+            if self.per_chain is None:
+                raise ValueError(f'{what}: weights="cold" needs a per_chain table (the cold slot '
+                                 "is the one with the smallest nd)")
+            slots = self.cold_slots()
+            w = torch.zeros(self.K, dtype=torch.float64)
+            w[slots] = 1.0 / len(slots)
+            w = w.to(self.args.device)
+        else:
+            if self.stacking_ is None:
+                raise ValueError(f'{what}: weights="stacking" needs a fit_stacking() first')
+            w = self.stacking_
         comps = max(1, len(self._component_keys()))
-        w = (self.stacking_ / comps).repeat(comps)  # [components, K] row-major
+        w = (w / comps).repeat(comps)  # [components, K] row-major
         return w.reshape(-1, 1).contiguous()
 
     def _report_stacking(self, ep, rec, val_loader, test_loader, log):
@@ -2024,6 +2192,8 @@ class _StackedSampler:
                     self._report_stacking(ep, rec, self.stacking_val, test_loader, log)
                 if self.per_chain is not None:
                     self._report_chains(ep, rec, test_loader, log)
+                if self.exchange_every:  # opt-in (run.py --exchange)
+                    self._report_exchange(ep, rec, log)
                 if getattr(self.args, "rhat", False):  # opt-in (run.py --rhat)
                     self._report_rhat(ep, rec, log)
                 if self.ess_batch:  # opt-in (run.py --ess)
@@ -2245,6 +2415,7 @@ class StackedSGLD(_StackedSampler):
     need_prior = True
     tune_method = "sgld"
     per_chain_family = "sgld"
+    exchange_ok = True  # momentum 0: chain k samples exp(-U / nd_k^2)
 
     def __init__(self, net, K_, args, **kw):
         super().__init__(net, K_, args, **kw)
@@ -2360,11 +2531,12 @@ class StackedSGLD(_StackedSampler):
 
     def _extra_state(self):
         return {"m1": self.m1, "m2": self.m2, "cnt": self.cnt, "bi": self.bi,
-                "has_buffer": self.has_buffer}
+                "has_buffer": self.has_buffer, **self._exchange_ckpt()}
 
     def _load_extra_state(self, d):
         self.m1, self.m2 = d["m1"], d["m2"]
         self.cnt, self.bi, self.has_buffer = d["cnt"], d["bi"], d["has_buffer"]
+        self._load_exchange_ckpt(d)
 
 
 class StackedCSGLD(StackedSGLD):
@@ -2455,13 +2627,14 @@ class StackedCSGLD(StackedSGLD):
     def _extra_state(self):
         return {"samples_per_cycle": dict(self.samples_per_cycle), "mom1": dict(self.mom1),
                 "mom2": dict(self.mom2), "has_buffer": self.has_buffer,
-                "epoch": self.sched.current_epoch, **self._gmm_state()}
+                "epoch": self.sched.current_epoch, **self._gmm_state(), **self._exchange_ckpt()}
 
     def _load_extra_state(self, d):
         self.samples_per_cycle = dict(d["samples_per_cycle"])
         self.mom1, self.mom2 = dict(d["mom1"]), dict(d["mom2"])
         self.has_buffer, self.sched.current_epoch = d["has_buffer"], d["epoch"]
         self._load_gmm_state(d)
+        self._load_exchange_ckpt(d)
 
 
 class StackedSGHMC(StackedSGLD):
@@ -2472,6 +2645,7 @@ class StackedSGHMC(StackedSGLD):
     moments.  `args` as the sghmc Runner's (hparams with momentum_decay)."""
 
     per_chain_family = None  # no per-chain SGHMC launch
+    exchange_ok = False       # and no temperature is derived for it
 
     def __init__(self, net, K_, args, **kw):
         super().__init__(net, K_, args, **kw)
@@ -2504,6 +2678,7 @@ class _AdamStep:
 
     tune_method = "adam"
     per_chain_family = None  # no per-chain Adam launch
+    exchange_ok = False       # and no temperature is derived for it
     grad_is_mom = False  # the cyclical variant's p.grad = v_mom (adam_csghmc.py:834)
 
     def _init_adam(self):
